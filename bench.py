@@ -1,6 +1,15 @@
 """Headline benchmark: training rays/s (fwd+bwd) of the HashNeRF step.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4|5]
+                    [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K steps and prints the headline
+line (value, ms_per_step, the workload).  --dump-outputs DIR then writes what
+the last timed step computed as DIR/<name>.npy (dump_outputs).  --full adds
+everything measured beside the headline, after the timed steps: the launch
+times and the roofline / MFMA / sparsity / exchange fields built on them, the
+host's enqueue time, and the CPU baseline (the oracle's training step on the
+host cores).
 
 N = 1 runs BASELINE.json configs[1] (chair, N_rand 4096, 64+128 samples,
 L=16 F=2 T=2^19 finest 512) on one MI355X.  N > 1 is launched by torchrun
@@ -317,6 +326,41 @@ def launch_ranks(n, argv):
     return subprocess.call(cmd)
 
 
+DUMP_TABLE_ROWS = 1 << 16        # table rows per level in --dump-outputs (the same rows every run)
+DUMP_RAY_BYTES = 48 * 10 ** 6    # budget of the per-ray arrays (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, tr, loss, mse, last):
+    """--dump-outputs: what the last timed Trainer.step() computed, as
+    <path>/<name>.npy in float32 -- the step's return values (loss, mse), the
+    parameters it left behind (the ten NeRFSmall weights; of the hash table
+    DUMP_TABLE_ROWS rows per level, drawn once from a fixed seed) and its
+    forward's per-ray results (functional.LAST: the z values and raw network
+    outputs of both passes; a fixed seeded subset of the rays if they would
+    exceed DUMP_RAY_BYTES).  The inputs (scene, initial weights, every random
+    draw) follow from the arguments alone, so two builds run with the same
+    arguments can be compared file by file."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    rng = np.random.Generator(np.random.PCG64(0))
+    arrays = {"loss": loss.detach().reshape(1), "mse": mse.detach().reshape(1)}
+    for net, ws in (("coarse", tr._ws[:5]), ("fine", tr._ws[5:])):
+        for k, w in zip(("sigma0", "sigma1", "color0", "color1", "color2"), ws):
+            arrays[f"{net}_{k}"] = w.detach()
+    table = tr.embed_fn.table.detach()
+    rows = np.sort(rng.choice(table.shape[1], size=min(DUMP_TABLE_ROWS, table.shape[1]), replace=False))
+    arrays["table_rows"] = table[:, torch.as_tensor(rows, device=table.device)]
+    per_ray = sum(last[k][0].numel() * 4 for k in last)
+    B = next(iter(last.values())).shape[0]
+    keep = min(B, DUMP_RAY_BYTES // per_ray)
+    sel = None if keep == B else torch.as_tensor(np.sort(rng.choice(B, size=keep, replace=False)))
+    for k, t in last.items():
+        arrays[k] = t if sel is None else t[sel.to(t.device)]
+    for k, t in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), t.to(dtype=torch.float32, device="cpu").numpy())
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=None,
@@ -325,7 +369,12 @@ def main():
     ap.add_argument("--warmup", type=int, default=5)
     ap.add_argument("--config", type=int, default=None, choices=sorted(CONFIGS))
     ap.add_argument("--n-rand", type=int, default=None)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the launch times (roofline, MFMA, exchange), the "
+                         "host's enqueue time, the sparsity and the CPU baseline, and add them to the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32; dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full without the CPU baseline")
     # the default workload is the chair stand-in in its trained regime: 1000
     # untimed steps first (~2 s), so the timed steps see the sample
     # distribution of most of a 5k-iteration run rather than of the first
@@ -335,9 +384,9 @@ def main():
     ap.add_argument("--pretrain", type=int, default=1000,
                     help="untimed training steps before warmup")
     ap.add_argument("--kernel-steps", type=int, default=5,
-                    help="steps after the timed region whose launches are timed with HIP events (roofline)")
+                    help="--full: steps after the timed region whose launches are timed with HIP events (roofline)")
     ap.add_argument("--cpu-steps", type=int, default=3,
-                    help="timed oracle steps of the CPU baseline, each at the config's N_rand")
+                    help="--full: timed oracle steps of the CPU baseline, each at the config's N_rand")
     ap.add_argument("--ray-order", type=int, default=1, choices=(0, 1),
                     help="batch order from the sampler: 1 Morton order of the pixels, 0 draw order")
     ap.add_argument("--dense-table-step", action="store_true",
@@ -361,6 +410,8 @@ def main():
     if args.config == 1:                      # the CPU path: no GPU touched
         if (args.gpus or 1) > 1:
             raise SystemExit("bench.py --config 1 is the CPU path (one process)")
+        if args.dump_outputs:
+            raise SystemExit("bench.py --dump-outputs writes the HIP trainer's outputs (configs 2-5)")
         return bench_config1(args)
     if "WORLD_SIZE" not in os.environ and (args.gpus or 1) > 1:
         sys.exit(launch_ranks(args.gpus, sys.argv[1:]))
@@ -429,7 +480,10 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     # the timed region carries no event records (an event pair idles the
-    # device ~10 us): the kernels' launch times come from the steps after it
+    # device ~10 us): --full takes the kernels' launch times from steps after it
+    # --dump-outputs: the forward keeps a reference to its last call's z
+    # values and raw outputs (functional.LAST; nothing is copied or computed)
+    HF.DEBUG_KEEP = bool(args.dump_outputs)
     t0 = time.perf_counter()
     for _ in range(args.steps):
         loss, mse = tr.step()
@@ -438,11 +492,48 @@ def main():
         dist.barrier()
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    HF.DEBUG_KEEP = False
     HF.L.check_device_faults()                # after the timed region: one blocking read
     t = torch.tensor([dt], device=dev)
     if world > 1:
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, tr, loss, mse, dict(HF.LAST))
+    B = cfg["N_rand"]
+    value = world * B * args.steps / dt
+    line = {
+        "metric": "training rays/sec (fwd+bwd) on chair; PSNR@5k iters",
+        "value": round(value, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
+        "warmup": args.warmup, "ms_per_step": round(dt * 1e3 / args.steps, 3),
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
+        # encoding, composite, losses, optimizer and every accumulation in f32; the
+        # NeRFSmall GEMMs run on the bf16 MFMA with f32 operands split into bf16
+        # parts: 3 in the forward (f32-accurate), 2 (~2^-17) in the gradients
+        "dtype": "fp32 (MLP GEMMs split-bf16 MFMA: 3 parts fwd, 2 parts grads)",
+        "data": ("synthetic: 100 blender-style 400x400 cameras, " +
+                 ("uniform random targets" if args.scene == "uniform" else
+                  f"procedural chair images (train.procedural_field, rendered in {t_data:.1f} s)") +
+                 (f", timed after {args.pretrain} untimed training steps" if args.pretrain else "")),
+        "config": {"workload": cfg["workload"], "rays_per_gpu": B, "global_batch": B * world,
+                   "samples_per_ray": "64+128", "log2_hashmap_size": cfg["log2_hashmap_size"],
+                   "finest_res": cfg["finest_res"], "parallelism": f"dp{world}"},
+        "loss": round(float(loss.item()), 6),
+    }
+    if args.full:
+        full = full_fields(args, cfg, cfg_id, tr, HF, dev, rank, world, value)
+        if rank == 0:
+            line.update(full)
+    if rank == 0:
+        print(json.dumps(line), flush=True)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def full_fields(args, cfg, cfg_id, tr, HF, dev, rank, world, value):
+    """--full: what the line carries beside the headline, measured on further
+    steps of the same training loop after the timed region (every rank runs
+    them; rank 0 returns the fields, the others None)."""
     # ONE timer for every launch time in the line: HIP events on the launch
     # stream around the forward and the backward launches (the deferred owner
     # pass of world > 1 included) of args.kernel_steps further steps, the same
@@ -494,30 +585,15 @@ def main():
         "on tiles without density (hn_render_cfg.dense_bwd = 0, skip_dead_color): every output and "
         "gradient as computed densely (tests/test_gpu_driver.py::test_zero_gradient_skip_bitwise)"}
     B = cfg["N_rand"]
-    value = world * B * args.steps / dt
+    line = None
     if rank == 0:
-        scatter = "binned" if HF.L.lib().hn_render_scatter_mode(tr._cfg, B) == 2 else "atomic"
+        scatter ="binned" if HF.L.lib().hn_render_scatter_mode(tr._cfg, B) == 2 else "atomic"
         traffic, traffic_src, atomics, pmc = measured_traffic(cfg_id, args.n_rand, args.scene, args.pretrain,
                                                               scatter)
         bwd_gbs = B * BWD_BYTES_PER_RAY / (bwd_ms * 1e-3) / 1e9 if bwd_ms > 0 else 0.0
         fwd_gbs = B * FWD_BYTES_PER_RAY / (fwd_ms * 1e-3) / 1e9 if fwd_ms > 0 else 0.0
         path_gbs = value / world * PATH_BYTES_PER_RAY / 1e9
         line = {
-            "metric": "training rays/sec (fwd+bwd) on chair; PSNR@5k iters",
-            "value": round(value, 1), "unit": "rays/s", "n_gpus": world, "steps": args.steps,
-            "warmup": args.warmup, "ms_per_step": round(dt * 1e3 / args.steps, 3),
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
-            # encoding, composite, losses, optimizer and every accumulation in f32; the
-            # NeRFSmall GEMMs run on the bf16 MFMA with f32 operands split into bf16
-            # parts: 3 in the forward (f32-accurate), 2 (~2^-17) in the gradients
-            "dtype": "fp32 (MLP GEMMs split-bf16 MFMA: 3 parts fwd, 2 parts grads)",
-            "data": ("synthetic: 100 blender-style 400x400 cameras, " +
-                     ("uniform random targets" if args.scene == "uniform" else
-                      f"procedural chair images (train.procedural_field, rendered in {t_data:.1f} s)") +
-                     (f", timed after {args.pretrain} untimed training steps" if args.pretrain else "")),
-            "config": {"workload": cfg["workload"], "rays_per_gpu": B, "global_batch": B * world,
-                       "samples_per_ray": "64+128", "log2_hashmap_size": cfg["log2_hashmap_size"],
-                       "finest_res": cfg["finest_res"], "parallelism": f"dp{world}"},
             "roofline": {"bound": "hbm",
                          "kernel": "render_bwd (hn_render_bwd launch: " + " + ".join(BWD_KERNELS[scatter]) + ")",
                          "achieved": round(bwd_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
@@ -553,7 +629,6 @@ def main():
                                                pmc=mfma_busy(pmc, "render_bwd_kernel", traffic_src))},
             "mlp_math": ("NeRFSmall GEMMs on v_mfma_f32_32x32x16_bf16 with f32 operands split into bf16 "
                          "parts: 3 parts in the forward (f32-accurate), 2 in the data/weight gradients"),
-            "loss": round(float(loss.item()), 6),
         }
         opt_b = optimizer_bytes(tr) if (world == 1 and tr.fuse_table_step and scatter == "binned") else 0
         if opt_b:
@@ -584,9 +659,7 @@ def main():
             line["exchange"] = xchg
         if world == 1 and not args.no_cpu_baseline:
             line["cpu_baseline"] = cpu_baseline(cfg, steps=args.cpu_steps)
-        print(json.dumps(line), flush=True)
-    if world > 1:
-        dist.destroy_process_group()
+    return line
 
 
 if __name__ == "__main__":

@@ -11,7 +11,7 @@ run() {   # name lib flags -> env for the library
 for r in $(seq 1 ${REPS:-2}); do
   for V in "$@"; do
     IFS=: read -r N LIBF FL <<< "$V"
-    env $(run $N $LIBF) timeout -k 10 300 python bench.py --steps ${STEPS:-50} --warmup 5 --no-cpu-baseline $FL > $O/${N}_$r.json 2> $O/${N}_$r.err || { tail -5 $O/${N}_$r.err; exit 1; }
+    env $(run $N $LIBF) timeout -k 10 300 python bench.py --steps ${STEPS:-50} --warmup 5 --full --no-cpu-baseline $FL > $O/${N}_$r.json 2> $O/${N}_$r.err || { tail -5 $O/${N}_$r.err; exit 1; }
     python -c "import json;d=json.load(open('$O/${N}_$r.json'));print('$N', $r, d['value'], d['ms_per_step'], d['kernels']['render_fwd_ms'], d['kernels']['render_bwd_ms'])"
   done
 done

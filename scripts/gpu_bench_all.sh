@@ -10,7 +10,7 @@ O=gpurun_out/$TAG
 mkdir -p $O
 export TMPDIR=/tmp
 for C in $CFGS; do
-  timeout -k 10 600 python bench.py --config $C > $O/bench_config${C}.json 2> $O/bench_config${C}.err \
+  timeout -k 10 600 python bench.py --full --config $C > $O/bench_config${C}.json 2> $O/bench_config${C}.err \
       || { tail -5 $O/bench_config${C}.err; exit 1; }
   python -c "import json;d=json.load(open('$O/bench_config${C}.json'));print('config $C', d['value'], d['ms_per_step'], d['kernels']['render_fwd_ms'], d['kernels']['render_bwd_ms'], d.get('cpu_baseline',{}).get('value'))"
 done

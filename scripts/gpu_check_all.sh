@@ -13,9 +13,9 @@ timeout -k 10 900 python -u -m pytest tests -m gpu -x -q -rf --timeout 170 --tim
 tail -3 $O/pytest_gpu.log; [ $RC -eq 0 ] || exit $RC
 timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $O/smoke.txt 2>&1 || { tail -5 $O/smoke.txt; exit 1; }
 tail -1 $O/smoke.txt
-timeout -k 10 600 python bench.py > $O/bench_full.json 2> $O/bench_full.err || { tail -5 $O/bench_full.err; exit 1; }
+timeout -k 10 600 python bench.py --full > $O/bench_full.json 2> $O/bench_full.err || { tail -5 $O/bench_full.err; exit 1; }
 cut -c1-300 $O/bench_full.json
-timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o prof -- python3 bench.py --steps 10 --warmup 3 --no-cpu-baseline > $O/prof.log 2>&1 || { tail -5 $O/prof.log; exit 1; }
+timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o prof -- python3 bench.py --steps 10 --warmup 3 --full --no-cpu-baseline > $O/prof.log 2>&1 || { tail -5 $O/prof.log; exit 1; }
 F=$(find $O/prof -name "*kernel_trace.csv" | head -1)
 python3 scripts/trace_tail_stats.py $F 20 > $O/kernel_stats_$TAG.csv
 S=$(find $O/prof -name "*kernel_stats.csv" | head -1); cp $S $O/rocprof_kernel_stats_$TAG.csv; rm -rf $O/prof
