@@ -1,0 +1,1279 @@
+// hn_bwd_binned.h -- the binned backward schedule (kModeSplit): every
+// benchmark line and nearly every test runs it.  Its kernels, in launch
+// order after render_comp_bwd_kernel's pre-pass:
+//   render_lists_kernel   lists of the 16-sample groups with a nonzero d raw
+//   render_bwd_kernel     <kSwVmcnt, kModeSplit>: 1,024 waves on equal slices
+//                         of the coarse and fine lists (b1_groups), feature
+//                         grads stored per point, one dW slab per run of waves
+//   scatter_bins_kernel   the feature grads as records per bin (run heads'
+//                         x-pairs, staged through LDS), the TV term's
+//                         records, then the dW slabs' reduction with the
+//                         NeRFSmall RAdam steps
+//   ovf_place_kernel      spilled records bucketed by bin (+ the repack)
+//   bin_reduce_kernel     the owner pass: exact fixed-point sums per bin, the
+//                         table gradient written once, or the fused table step
+// No float atomic reaches memory and every sum has a fixed order, so the
+// gradients are bitwise reproducible.
+#pragma once
+#include "hn_mlp_bwd.h"
+
+namespace hn {
+
+// ---- binned table-gradient scatter ------------------------------------------
+// The memory-side float-atomic rate (~20 G requests/s, one per 64-B segment
+// of a wave-instruction) bounds the atomic scatter.  The binned scatter sends
+// no float atomic to memory: each run head's x-pair of a corner row becomes
+// one 20-B record {4 sums: (x0 f0, x0 f1, x1 f0, x1 f1), entry word}, written
+// into the region of its bin (2^bin_shift consecutive table entries,
+// level-major); bin_reduce_kernel then owns each bin and writes its slice of
+// the gradient once.  Entry word = (l << T) + h(x0) | nbits << 28: the x1
+// corner's row is h(x0) ^ ((2^nbits - 1) & mask), since the x prime is 1 and
+// x1 = x0 + 1 differs from x0 in its trailing ones and the bit above (nbits
+// <= 11 for cells <= 1024, so both rows fall in one 2^13-entry bin).
+// Layout (floats from bins): vals f32x4 [nbins][kBwdBlocks][cap] (a bin's
+// regions are contiguous for its owner) then the overflow lists
+// [kBwdBlocks][ovf_per_block]; idx u32 over the same record index; counts u32
+// [nbins][kBwdBlocks]; largest |value| per level f32 [16][kBwdBlocks] (the
+// owner's fixed-point scale); then the overflow book (OvfBook).  The producer
+// counts its records per bin in LDS (ds_add_rtn); a record past its region's
+// capacity goes to the block's own overflow list (one more LDS counter), so
+// spilling costs no global atomic.  A block's list holds every record the
+// block can make (64 samples x 16 levels x 4 corner rows per unit): clumped
+// input (a scene box inside the sample range, where every out-of-box sample
+// clamps onto the box surface; the coarse levels of a T = 22 table) spills
+// but never runs out.  ovf_place_kernel buckets the spilled records by bin so
+// that each owner reads only its own.
+
+// Record r in memory: the values [nrec] f32x4 then the words [nrec] u32.
+// Measured and removed (round 2): groups of 4 records = 4 value quads
+// then their 4 entry words (80 B), a record's value and word in one line and
+// one write stream per region -- measured slower on config 2 (scatter +5 us,
+// owner +6.5 us, two A/B pairs on one box): the owner's value loads then span
+// 80-B strides instead of dense 1-KiB runs.  Either way the records take
+// 5 * nrec floats from `bins` and the book words follow at bins + 5 * nrec
+// (ovf_book's idx base = bins + 4 * nrec).
+HN_DEV size_t rec_vofs(size_t r) { return 4 * r; }
+HN_DEV size_t rec_wofs(size_t r, size_t nrec) { return 4 * nrec + r; }
+// A record store.  The staged pool's runs of records (whole lines, read
+// once by the owner pass) are written nontemporally; the direct stores (partial
+// lines, scattered over the regions) go through L2 as usual, where their
+// lines fill up.  Measured (config 2): direct stores nontemporal too, scatter
+// 0.197 -> 0.321 ms; staged runs only, scatter and owner both faster (the L2s
+// hold fewer dirty record lines to write back).
+template <bool kStaged = false>
+HN_DEV void rec_put(float* bins, size_t r, size_t nrec, f32x4 v, uint32_t w) {
+  f32x4* pv = reinterpret_cast<f32x4*>(bins + rec_vofs(r));
+  uint32_t* pw = reinterpret_cast<uint32_t*>(bins) + rec_wofs(r, nrec);
+  if (kStaged) {
+    __builtin_nontemporal_store(v, pv);
+    __builtin_nontemporal_store(w, pw);
+  } else {
+    *pv = v;
+    *pw = w;
+  }
+}
+struct BinW {
+  float* bins;
+  size_t nrec;
+  unsigned long long* lcnt;   // LDS [nbins]: records of the bin (low 32 bits: the slot
+                              // counter), records of it in the current staging phase (high 32)
+  uint32_t* lovf;      // LDS: this block's overflow records
+  size_t base;         // first record of this block's region of bin 0
+  size_t stride;       // records between a block's regions of consecutive bins
+  size_t ovf_base;     // first record of this block's overflow list
+  uint32_t n_ovf;      // its length
+  uint32_t cap, shift;
+};
+
+__host__ __device__ inline int64_t sc_units_per_block(int64_t n_rays) {   // scatter_bins_kernel: 3 units per ray
+  return (3 * (n_rays > 0 ? n_rays : 1) + kBwdBlocks - 1) / kBwdBlocks;
+}
+// TV records (the scatter blocks' share of the x-pairs, cubes <= kTvRecMaxCube):
+// at most L x ((c + 2) / 2) x (c + 1)^2 pairs over the 256 blocks
+constexpr int kTvRecMaxCube = 50;
+constexpr size_t kTvRecPerBlock = (16 * ((kTvRecMaxCube + 2) / 2) * (kTvRecMaxCube + 1) * (kTvRecMaxCube + 1) +
+                                   kBwdBlocks - 1) / kBwdBlocks;
+// a producer's overflow list holds everything it can write: its units' render
+// records (64 samples x 16 levels x 4 corner rows each) plus its TV share
+__host__ __device__ inline size_t ovf_per_block(int64_t n_rays) {
+  return (size_t)sc_units_per_block(n_rays) * 64 * 64 + kTvRecPerBlock;
+}
+__host__ __device__ inline size_t bin_records(int nbins, int cap, int64_t n_rays) {
+  return (size_t)kBwdBlocks * nbins * cap + (size_t)kBwdBlocks * ovf_per_block(n_rays);
+}
+// Overflow book, u32 words after the counts and level maxima (idx + nrec +
+// kBwdBlocks * (nbins + 16)): total spilled, spilled per bin, placement
+// cursors, first slot per bin, the scatter blocks' slab-block counter,
+// spilled per producer block, record ids (relative to the first overflow
+// record) bucketed by bin.  All of it lives in the call's workspace, so
+// concurrent hn_render_bwd calls with their own workspaces share nothing.
+struct OvfBook {
+  uint32_t *cnt, *per_bin, *cur, *first, *slab_next, *blk, *ids;
+};
+__host__ __device__ inline size_t ovf_book_words(int nbins, int64_t n_rays) {
+  return 2 + 3 * (size_t)nbins + kBwdBlocks + (size_t)kBwdBlocks * ovf_per_block(n_rays);
+}
+__host__ __device__ inline OvfBook ovf_book(uint32_t* idx, size_t nrec, int nbins) {
+  OvfBook o;
+  o.cnt = idx + nrec + (size_t)kBwdBlocks * (nbins + 16);
+  o.per_bin = o.cnt + 1;
+  o.cur = o.per_bin + nbins;
+  o.first = o.cur + nbins;
+  o.slab_next = o.first + nbins;
+  o.blk = o.slab_next + 1;
+  o.ids = o.blk + kBwdBlocks;
+  return o;
+}
+
+// max(|a|, |b|, m) for m >= 0 as one v_max3_f32 with abs modifiers: the
+// compiler's fmaxf in IEEE mode first quiets each input (v_max_f32 x, x), two
+// extra instructions per value.  Plain VALU operands (no MFMA or DPP result
+// read here), so the asm needs no hazard padding; the values are finite (a
+// non-finite one has already set the fault bit).
+HN_DEV float max3_abs(float a, float b, float m) {
+  float r;
+  asm("v_max3_f32 %0, |%1|, |%2|, %3" : "=v"(r) : "v"(a), "v"(b), "v"(m));
+  return r;
+}
+
+// Segmented suffix sum over runs of samples in one voxel along a 16-lane
+// DPP row: lane pp absorbs lane pp + d iff no
+// run head lies in (pp, pp + d]; pm = the row's head mask.  s1..s8:
+// wave-uniform "some run is longer than 1 / 2 / 4 / 8" (steps skipped when
+// no row needs them; a lane whose row does not, absorbs nothing).
+// v + (same ? o : 0) is computed as fma(o, same, v): fma(o, 1, v) rounds
+// like v + o, and fma(o, 0, v) = v (up to the sign of a zero v, which no
+// record value carries into the owner's integer sums).
+// All 4 corner rows of a level at once (the runs, and so `same`, are the
+// rows' common ones), each step 16 v_fmac_f32_dpp: left to the compiler, the
+// fma is packed into v_pk_fma_f32, which cannot take a DPP source, with a
+// v_mov_b32_dpp per value (r05: scatter 0.213 -> 0.202 ms).
+#define HN_SEG_FMAC(C, E, D) \
+  "v_fmac_f32_dpp %[v" #C #E "], %[v" #C #E "], %[sf] row_shl:" #D " row_mask:0xf bank_mask:0xf bound_ctrl:1\n"
+// The steps as one asm block with wave-uniform branches inside (n = steps
+// to run): the 16 values enter and leave once, without the copies the
+// compiler puts at the joins of separately branched blocks.  Step d's `same`
+// is computed in the block (v_cmp writes vcc, s_nop 1 before the v_cndmask
+// reads it, as the compiler does); its 4 instructions also give the first
+// DPP read its 2 wait states.
+#define HN_SEG_SAME(M)                                                                                       \
+  "v_lshrrev_b32 %[t], %[sh], %[pm]\n"                                                                       \
+  "v_and_b32 %[t], " #M ", %[t]\n"                                                                           \
+  "v_cmp_eq_u32 vcc, 0, %[t]\n"                                                                              \
+  "s_nop 1\n"                                                                                                \
+  "v_cndmask_b32_e64 %[sf], 0, 1.0, vcc\n"
+#define HN_SEG_BODY(D)                                                                                       \
+  HN_SEG_FMAC(0, 0, D) HN_SEG_FMAC(0, 1, D) HN_SEG_FMAC(0, 2, D) HN_SEG_FMAC(0, 3, D) HN_SEG_FMAC(1, 0, D)    \
+  HN_SEG_FMAC(1, 1, D) HN_SEG_FMAC(1, 2, D) HN_SEG_FMAC(1, 3, D) HN_SEG_FMAC(2, 0, D) HN_SEG_FMAC(2, 1, D)    \
+  HN_SEG_FMAC(2, 2, D) HN_SEG_FMAC(2, 3, D) HN_SEG_FMAC(3, 0, D) HN_SEG_FMAC(3, 1, D) HN_SEG_FMAC(3, 2, D)    \
+  HN_SEG_FMAC(3, 3, D)
+HN_DEV void seg_sum16(float (&v)[4][4], uint32_t pm, int pp, bool s1, bool s2, bool s4, bool s8) {
+  // wave-uniform (from ballots); readfirstlane keeps it in an SGPR
+  const int n = __builtin_amdgcn_readfirstlane(s1 ? (s2 ? (s4 ? (s8 ? 4 : 3) : 2) : 1) : 0);
+  float t, sf;
+  asm("s_cmp_eq_u32 %[n], 0\n s_cbranch_scc1 Lseg_end%=\n"
+      HN_SEG_SAME(1) HN_SEG_BODY(1)
+      "s_cmp_eq_u32 %[n], 1\n s_cbranch_scc1 Lseg_end%=\n"
+      HN_SEG_SAME(3) HN_SEG_BODY(2)
+      "s_cmp_eq_u32 %[n], 2\n s_cbranch_scc1 Lseg_end%=\n"
+      HN_SEG_SAME(15) HN_SEG_BODY(4)
+      "s_cmp_eq_u32 %[n], 3\n s_cbranch_scc1 Lseg_end%=\n"
+      HN_SEG_SAME(0xff) HN_SEG_BODY(8)
+      "Lseg_end%=:\n"
+      : [v00] "+v"(v[0][0]), [v01] "+v"(v[0][1]), [v02] "+v"(v[0][2]), [v03] "+v"(v[0][3]),
+        [v10] "+v"(v[1][0]), [v11] "+v"(v[1][1]), [v12] "+v"(v[1][2]), [v13] "+v"(v[1][3]),
+        [v20] "+v"(v[2][0]), [v21] "+v"(v[2][1]), [v22] "+v"(v[2][2]), [v23] "+v"(v[2][3]),
+        [v30] "+v"(v[3][0]), [v31] "+v"(v[3][1]), [v32] "+v"(v[3][2]), [v33] "+v"(v[3][3]),
+        [t] "=&v"(t), [sf] "=&v"(sf)
+      : [n] "s"(n), [sh] "v"((uint32_t)pp + 1u), [pm] "v"(pm)
+      : "vcc", "scc");
+}
+#undef HN_SEG_SAME
+#undef HN_SEG_BODY
+#undef HN_SEG_FMAC
+
+// round(v * 2^S) as int64 without f64 arithmetic: x = v * 2^S is exact in fp32
+// (|x| < 2^47, a power-of-2 scale), a = trunc(x / 2^16) is an exact integer
+// (|a| < 2^31),
+// b = x - a * 2^16 exact with |b| < 2^16, and round(x) = a * 2^16 + rint(b)
+// (ties to even agree: a * 2^16 is even).
+HN_DEV long long fx_of(float v, float scale) {
+  const float x = v * scale;
+  const float a = truncf(x * 0x1p-16f);
+  const float b = __builtin_fmaf(-a, 0x1p16f, x);
+  return ((long long)(int32_t)a << 16) + (long long)(int32_t)rintf(b);
+}
+
+// A run head's record: the x-pair (x0 = cx, x1 = cx + 1) of corner row (yy, zz)
+// (the y / z coordinates times their primes) at level l.  rec_slot takes the
+// record's slot in its bin (LDS counter); rec_store writes it -- split so a
+// caller can have several counter round trips in flight.
+struct RecSlot {
+  uint32_t word, bin, slot, pj;   // pj: the record's index among the bin's records of the staging phase
+};
+// staged = count the record in the bin's staging-phase half too (one 64-bit
+// LDS add returns both counts: the staging index needs no separate read of
+// the phase's first slot)
+constexpr unsigned long long kCntRec = 1ull, kCntStaged = (1ull << 32) | 1ull;
+HN_DEV RecSlot rec_slot(const BinW& bw, uint32_t l, uint32_t log2T, uint32_t cx, uint32_t yy, uint32_t zz,
+                        unsigned long long inc = kCntRec) {
+  const uint32_t mask = (1u << log2T) - 1u;
+  const uint32_t flat = (l << log2T) + ((cx ^ yy ^ zz) & mask);
+  const uint32_t nbits = (uint32_t)__builtin_ctz(~cx) + 1u;
+  RecSlot r;
+  r.word = flat | (nbits << 28);
+  r.bin = flat >> bw.shift;
+  const unsigned long long old =
+      __hip_atomic_fetch_add(bw.lcnt + r.bin, inc, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  r.slot = (uint32_t)old;
+  r.pj = (uint32_t)(old >> 32);
+  return r;
+}
+HN_DEV void rec_store(const BinW& bw, const RecSlot& rs, const float (&v)[4]) {
+  size_t r = bw.base + (size_t)rs.bin * bw.stride + rs.slot;
+  bool ok = true;
+  if (rs.slot >= bw.cap) {
+    const uint32_t o = __hip_atomic_fetch_add(bw.lovf, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    ok = o < bw.n_ovf;   // always, by the list's size
+    r = bw.ovf_base + o;
+    if (!ok) __hip_atomic_fetch_or(&g_hn_fault, kFaultBins, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (ok) {
+    rec_put(bw.bins, r, bw.nrec, f32x4{v[0], v[1], v[2], v[3]}, rs.word);
+  }
+}
+
+// Voxel of one (point, level) for the split scatter: the cell from cell_floor
+// (the forward's), the weights by the reference's IEEE divisions.
+HN_DEV void voxel_cw_sc(const GridArgs& g, const float* gsl, const float pt[3], const float xc[3], int l,
+                        int32_t cell[3], float w[3]) {
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float gs = gsl[3 * l + a];
+    const int32_t i = cell_floor(xc[a] - g.bmin[a], gs, gsl[kGsRcp + 3 * l + a]);
+    const float vmin = (float)i * gs + g.bmin[a];
+    const float vmax = vmin + gs;
+    w[a] = div_rn(pt[a] - vmin, vmax - vmin);
+    cell[a] = i;
+  }
+}
+
+// ---- the table-gradient scatter as its own kernel --------------------------
+// render_bwd_kernel stores each tile's feature grads; scatter_bins_kernel
+// then runs the scatter at full occupancy (16 waves per CU).  A wave's unit is
+// four listed 16-sample groups (dense_bwd: a third of one ray's 192 fine
+// samples), lane = sample: its point o + d z, its grads (fine + coarse twin,
+// in that order), its voxel computed once per level; per corner row the
+// x-pair sums over runs of samples in one voxel (16-lane rows) and one record
+// per run head.  Block b is producer b of the record layout (kBwdBlocks
+// blocks).
+constexpr int kScWaves = 16;
+constexpr int kScMaxBinsLog2 = 13;
+constexpr int kScMaxBins = 1 << kScMaxBinsLog2;   // LDS counters (32 KiB): T <= 22 at 2^13 entries per bin
+constexpr int kBinShift = 13;   // preferred log2 entries per bin (bin_geom)
+
+// Record staging: level-major phases across the block's waves (all 16 waves
+// take level l of their units, then the block syncs), each head lane's record
+// put into an LDS pool at (bin of the level, slot - the bin's first slot of the
+// phase) and the pool flushed by the block in slot order: a bin's records of
+// the phase leave as contiguous runs (one 16-B value and one word per lane,
+// consecutive lanes on consecutive slots) instead of 64 scattered 16-B and 4-B
+// stores per instruction.  Records past the pool's share of their bin (2^kStLog2
+// records over the level's bins) or past the region's capacity are stored
+// directly.  The slot of every record is the same as without staging, so the
+// record buffer, and the owner's sums, are identical.  Measured (r03g, config
+// 2): WRITE_SIZE 548 -> 395 MB per launch for 352 MB of records (1.56x ->
+// 1.12x), backward launch time unchanged (0.813 / 0.814 vs 0.813 / 0.812 ms):
+// the scatter waits on its own dependency chains (SQ_WAIT_INST_ANY 44% of its
+// wave cycles), not on the write traffic.
+constexpr int kStLog2 = 12, kStPool = 1 << kStLog2;   // 64 KiB of values + 16 KiB of words
+constexpr int kStMinLog2C = 3;                          // fewer than 8 records per bin: no staging
+struct StPhase {
+  int b0, log2c;   // first bin of the phase's levels, log2 pool records per bin (< kStMinLog2C: direct)
+  int nbl;         // bins of the phase's levels
+};
+// a staging phase: levels l .. l + 2^lg2n - 1 (their bins are consecutive;
+// several levels per phase only where every level owns whole bins)
+HN_DEV StPhase st_phase(int l, int log2T, int shift, int lg2n = 0) {
+  StPhase ph;
+  ph.b0 = (int)(((uint32_t)l << log2T) >> shift);
+  const int lg = log2T > shift ? log2T - shift : 0;
+  ph.nbl = 1 << (lg + lg2n);
+  ph.log2c = kStLog2 - lg - lg2n;
+  return ph;
+}
+// log2 levels per staging phase where the pool still holds 8 records per bin
+// (one block barrier pair per phase; r05h: 1 level 0.984-0.987 ms per step,
+// 2: 0.988-1.005, 4: 1.012-1.014, 8: 1.037-1.039)
+constexpr int kScLpp = 1;
+
+__global__ __launch_bounds__(64 * kScWaves) void scatter_bins_kernel(ScK k) {
+  // dynamic LDS: the bins' record counters, then the staging pool
+  // (the host's BwdPlan::sc_lds)
+  extern __shared__ __attribute__((aligned(16))) uint32_t sc_dyn[];
+  unsigned long long* const bcnt = reinterpret_cast<unsigned long long*>(sc_dyn);   // BinW::lcnt
+  __shared__ float gsl[kGsLds], lvmx[16];
+  __shared__ uint32_t lovf;
+  __shared__ uint32_t lvmxl[16 * 64];
+  for (int i = threadIdx.x; i < 16 * 64; i += blockDim.x) lvmxl[i] = 0u;
+  // wave-uniform work-unit arithmetic (u, ray = u / 3, u % 3, act) on the scalar unit
+  const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6), lane = lane_id();
+  for (int i = threadIdx.x; i < k.nbins; i += blockDim.x) bcnt[i] = 0ull;
+  if (threadIdx.x < 16) lvmx[threadIdx.x] = 0.f;
+  if (threadIdx.x == 0) lovf = 0u;
+  stage_grid_sizes(k.g, gsl);
+  __syncthreads();
+  BinW bw;
+  const size_t nrec = bin_records(k.nbins, k.bin_cap, k.B);
+  bw.bins = k.bins;
+  bw.nrec = nrec;
+  uint32_t* const book = reinterpret_cast<uint32_t*>(k.bins + 4 * nrec);
+  const OvfBook ob = ovf_book(book, nrec, k.nbins);
+  bw.lovf = &lovf;
+  bw.n_ovf = (uint32_t)ovf_per_block(k.B);
+  bw.lcnt = bcnt;
+  bw.base = (size_t)blockIdx.x * k.bin_cap;
+  bw.stride = (size_t)kBwdBlocks * k.bin_cap;
+  bw.ovf_base = (size_t)kBwdBlocks * k.nbins * k.bin_cap + (size_t)blockIdx.x * bw.n_ovf;
+
+  bw.cap = (uint32_t)k.bin_cap;
+  bw.shift = (uint32_t)k.bin_shift;
+  // The block's units.  With exact-zero skipping: its slice of the list of
+  // fine 16-sample groups that have feature grads to scatter
+  // (render_lists_kernel, from the composite pre-pass's marks), the list in
+  // ray order and cut into equal slices over the blocks -- every block the
+  // same share of the work, whatever the scene leaves nonzero; a wave's unit
+  // is four consecutive groups of the slice, one per 16-lane run row (often of
+  // different rays; runs never cross rows, so the records are the dense
+  // form's).  Otherwise (dense_bwd) every unit is a third of one ray's fine
+  // samples, the rays permuted as the MLP backward's (unit_ray).
+  const bool use_list = k.slist != nullptr;
+  int64_t u0 = 0, u1 = 0;
+  int64_t s0 = 0, s1 = 0;   // this block's slice of the group list
+  if (use_list) {
+    const int64_t Ns = __builtin_amdgcn_readfirstlane(k.lmeta[2]);
+    s0 = (int64_t)blockIdx.x * Ns / gridDim.x;
+    s1 = (int64_t)(blockIdx.x + 1) * Ns / gridDim.x;
+    u1 = (s1 - s0 + 3) / 4;   // a unit = four consecutive groups of the slice, one per 16-lane row
+  } else {
+    const int64_t units = 3 * k.B;
+    const int64_t per = (units + gridDim.x - 1) / gridDim.x;
+    u0 = (int64_t)blockIdx.x * per;
+    u1 = u0 + per < units ? u0 + per : units;
+  }
+  const int pp = lane & 15;
+  // the staging pool: 80 KiB
+  uint32_t* const st_raw = sc_dyn + 2 * ((k.nbins + 3) & ~3);   // 16-B aligned after the counters
+  f32x4* const stv = reinterpret_cast<f32x4*>(st_raw);
+  uint32_t* const stw = st_raw + 4 * kStPool;
+  __shared__ uint32_t stfl[2][kStPool >> kStMinLog2C];   // per phase parity: first staged slot per bin
+  const int log2T = (int)k.g.log2T, sh = k.bin_shift;
+  // first staged slot of each bin of level l (the bins' counts so far, capped)
+  // (stfl alternates between phases: par = the phase's parity)
+  int par = 0;
+  auto st_init = [&](const StPhase& ph, int pr) {
+    if (ph.log2c < kStMinLog2C) return;
+    for (int i = threadIdx.x; i < ph.nbl; i += blockDim.x) {
+      const unsigned long long c = bcnt[ph.b0 + i];
+      stfl[pr][i] = min((uint32_t)c, bw.cap);
+      bcnt[ph.b0 + i] = c & 0xffffffffull;   // the phase's count from 0 (no atomics in flight on it now)
+    }
+  };
+  // the pool's records of level l to their regions, in slot order
+  auto st_flush = [&](const StPhase& ph) {
+    if (ph.log2c < kStMinLog2C) return;
+    const uint32_t c = 1u << ph.log2c;
+    for (int p = threadIdx.x; p < kStPool; p += blockDim.x) {
+      const int bl = p >> ph.log2c, b = ph.b0 + bl;
+      const uint32_t j = (uint32_t)p & (c - 1u), f = stfl[par][bl];
+      const uint32_t end = min(min((uint32_t)bcnt[b], bw.cap), f + c);
+      if (f + j < end) {
+        const size_t r = bw.base + (size_t)b * bw.stride + f + j;
+        rec_put<true>(bw.bins, r, bw.nrec, stv[p], stw[p]);
+      }
+    }
+  };
+  const int64_t n_it = (u1 - u0 + kScWaves - 1) / kScWaves;   // the same for every wave of the block
+  // one unit's inputs: its ray, point and (fine + coarse twin) grads of one level
+  struct Unit {
+    bool act;
+    Ray r;
+    float pt[3], xc[3];
+    const float* tb;   // the sample's fine grads (tile order), or null: exactly zero
+    const float* tw;   // its coarse twin's grads, or null (none, or exactly zero)
+    float g0, g1;      // the current level's two feature grads (fine + coarse twin)
+  };
+  bool bad = false;   // a non-finite grad or point seen by this lane
+  // dense_bwd: a fixed pseudo-random permutation of the batch (ScK::scramble),
+  // so the units without any gradient (below) spread evenly over the blocks
+  auto unit_ray = [&](int64_t j) -> int64_t {
+    uint32_t x = (uint32_t)j;
+    if (k.scramble) {
+      do {
+        x = feistel(x, k.scramble, 0x5bd1e995u);
+      } while ((int64_t)x >= k.B);
+    }
+    return (int64_t)x;
+  };
+  // unit u0 + wave + it * kScWaves: its ray, the lane's sample point and grad rows
+  auto unit_base = [&](int64_t it) {
+    Unit q;
+    const int64_t u = u0 + wave + it * kScWaves;
+    q.act = u < u1;
+    q.g0 = q.g1 = 0.f;
+    q.tb = q.tw = nullptr;
+    if (q.act) {
+      int64_t ray;
+      int i;   // the lane's fine sample
+      bool none = false;   // a second tile that does not exist: no grads
+      if (use_list) {
+        // row r of the unit: group s0 + 4 u + r, a group of 16 consecutive
+        // samples of one ray -- the run rows are the dense form's, so the
+        // records are too (minus the all-zero ones)
+        const int64_t gj = s0 + 4 * u + (lane >> 4);
+        const int c0 = k.slist[s0 + 4 * u];
+        const int code = gj < s1 ? k.slist[gj] : c0;
+        none = gj >= s1;
+        ray = code >> 4;
+        i = 16 * (code & 15) + (lane & 15);
+      } else {
+        ray = unit_ray(u / 3);
+        i = 64 * (int)(u % 3) + lane;
+      }
+      {
+        const float* rb = k.rays + 11 * ray;
+#pragma unroll
+        for (int a = 0; a < 3; ++a) {
+          q.r.o[a] = rb[a];
+          q.r.d[a] = rb[3 + a];
+        }
+      }
+      ray_point(q.r, k.z_fine[ray * kSf + i], q.pt);
+#pragma unroll
+      for (int a = 0; a < 3; ++a) q.xc[a] = clamp_t(q.pt[a], k.g.bmin[a], k.g.bmax[a]);
+      bad |= !(fabsf((q.pt[0] + q.pt[1]) + q.pt[2]) <= 3.402823466e38f);
+      // a sample whose d raw is exactly zero has exactly zero feature grads (the
+      // MLP backward did not store them: the lists' skip); the same for
+      // its coarse twin
+      const float* dr = k.draw + (size_t)ray * (kSc + kSf) * 4;
+      if (!none && (!k.skip_zero || draw_nonzero(*reinterpret_cast<const float4*>(dr + 4 * (kSc + i)))))
+        q.tb = k.dfeat_f + ((size_t)ray * (kSf / 32) + (i >> 5)) * 1024 + 4 * (i & 31);
+      const int src = k.fine_src[ray * kSf + i];
+      if (!none && src < kSc && (!k.skip_zero || draw_nonzero(*reinterpret_cast<const float4*>(dr + 4 * src))))
+        q.tw = k.dfeat_c + (size_t)ray * kDcRay + (size_t)(src >> 5) * 1024 + 4 * (src & 31);
+      // no lane with a gradient: the unit writes no record (wave-uniform)
+      q.act = __ballot(q.tb != nullptr || q.tw != nullptr) != 0ull;
+    }
+    return q;
+  };
+  // level l's grads = elements 2 (l & 1) .. of level pair l / 2 (tile_level:
+  // chunk lp / 2 of lane half lp % 2); a coarse twin adds its coarse grads
+  // (fine + twin, in that order); no twin: the fine grads as they are.  (Loading
+  // level l + 1's while level l runs measured no faster, r05g.)
+  auto unit_grads = [&](Unit& q, int l) {
+    if (!q.act) return;
+    const int lp = l >> 1, o = 4 * (64 * (lp >> 1) + 32 * (lp & 1)) + 2 * (l & 1);
+    float2 gq = q.tb ? *reinterpret_cast<const float2*>(q.tb + o) : make_float2(0.f, 0.f);
+    if (q.tw) {
+      const float2 t = *reinterpret_cast<const float2*>(q.tw + o);
+      gq = make_float2(gq.x + t.x, gq.y + t.y);
+    }
+    q.g0 = gq.x;
+    q.g1 = gq.y;
+    bad |= !(fabsf(gq.x + gq.y) <= 3.402823466e38f);
+  };
+  // The records of one level of a unit: voxel, run heads, per corner row the
+  // x-pair sums over runs of samples in one voxel (16-lane rows), then each
+  // head lane's record into the staging pool, or stored directly (slots from
+  // the LDS counters)
+  auto level = [&](const Unit& q, const int l, const StPhase& ph) {
+    if (!q.act) return;
+    const bool staged = ph.log2c >= kStMinLog2C;
+    int32_t cell[3];
+    float w[3];
+    voxel_cw_sc(k.g, gsl, q.pt, q.xc, l, cell, w);
+    const uint32_t cx = (uint32_t)cell[0], y0 = (uint32_t)cell[1] * kPrimeY, z0 = (uint32_t)cell[2] * kPrimeZ;
+    const uint32_t q0 = dpp_u<kRowShr1>(cx), q1 = dpp_u<kRowShr1>(y0), q2 = dpp_u<kRowShr1>(z0);
+    bool head = pp == 0 || q0 != cx || q1 != y0 || q2 != z0;
+    const uint64_t hb = __ballot(head);
+    const uint32_t pm = ((uint32_t)(hb >> (lane & 48)) & 0xffffu) | 0x10000u;   // + virtual head 16 (seg_same)
+    // lane 0 of every row is a head, so these never carry across rows
+    const uint64_t nz1 = ~hb & 0xfffefffefffefffeull, nz2 = nz1 & (nz1 >> 1), nz4 = nz2 & (nz2 >> 2);
+    const bool s1 = nz1 != 0ull, s2 = nz2 != 0ull, s4 = nz4 != 0ull, s8 = (nz4 & (nz4 >> 4)) != 0ull;
+    const float az = 1.f - w[2], ay = 1.f - w[1], ax = 1.f - w[0];
+    // d feat / d e_c = ((g * wz) * wy) * wx (trilerp_bwd's order)
+    // the two features as one packed pair (v_pk_mul_f32: the same fp32
+    // products, half the instructions; the asm below would otherwise leave
+    // them unpacked)
+    typedef float f2 __attribute__((ext_vector_type(2)));
+    const f2 g2 = {q.g0, q.g1};
+    const f2 gz[2] = {g2 * az, g2 * w[2]};   // [k] (features f0, f1)
+    float vmax = 0.f;   // largest |record value| of the level: the owner's fixed-point scale
+    float v[4][4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const int j = c >> 1, kk = c & 1;
+      const float wy = j ? w[1] : ay;
+      const f2 a = gz[kk] * wy;
+      const f2 x0 = a * ax, x1 = a * w[0];
+      v[c][0] = x0.x; v[c][1] = x0.y; v[c][2] = x1.x; v[c][3] = x1.y;
+    }
+    seg_sum16(v, pm, pp, s1, s2, s4, s8);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) vmax = max3_abs(v[c][2], v[c][3], max3_abs(v[c][0], v[c][1], vmax));
+    RecSlot rs[4];
+    // a run whose four sums are exactly zero (samples without gradient, or a
+    // zero trilinear weight) adds nothing to the owner's integer sums: no
+    // record (the same table gradient bitwise; not with dense_bwd)
+    bool put[4];
+#pragma unroll
+    for (int c = 0; c < 4; ++c)
+      put[c] = head && (!k.skip_zero || ((__float_as_uint(v[c][0]) | __float_as_uint(v[c][1]) |
+                                           __float_as_uint(v[c][2]) | __float_as_uint(v[c][3])) << 1) != 0u);
+    if (head) {
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {   // 4 counter round trips in flight
+        const int j = c >> 1, kk = c & 1;
+        if (put[c])
+          rs[c] = rec_slot(bw, (uint32_t)l, (uint32_t)log2T, cx, j ? y0 + kPrimeY : y0, kk ? z0 + kPrimeZ : z0,
+                           staged ? kCntStaged : kCntRec);
+      }
+#pragma unroll
+      for (int c = 0; c < 4; ++c) {
+        if (!put[c]) continue;
+        // staged index = the record's place among the bin's records of this
+        // phase (its slot minus the phase's first slot whenever slot < cap)
+        const uint32_t bl = rs[c].bin - (uint32_t)ph.b0, j = rs[c].pj;
+        if (staged && rs[c].slot < bw.cap && j < (1u << ph.log2c)) {
+          const int qq = (int)((bl << ph.log2c) + j);
+          stv[qq] = f32x4{v[c][0], v[c][1], v[c][2], v[c][3]};
+          stw[qq] = rs[c].word;
+          continue;
+        }
+        rec_store(bw, rs[c], v[c]);
+      }
+    }
+    __hip_atomic_fetch_max(&lvmxl[l * 64 + lane], __float_as_uint(vmax), __ATOMIC_RELAXED,
+                           __HIP_MEMORY_SCOPE_WORKGROUP);
+  };
+  // staging phases of 2^lpp levels where each level owns whole bins and the
+  // pool still holds >= 2^kStMinLog2C records per bin (T=19: 2 levels per
+  // phase, 32 records per bin; T=22: 1 level, 8 per bin)
+  const int lg_bins = log2T - sh;   // log2 bins per level
+  const int lpp = lg_bins < 0 ? 0 : max(0, min(kScLpp, kStLog2 - kStMinLog2C - lg_bins));
+  auto phase_of = [&](int l) { return st_phase(l, log2T, sh, l + (1 << lpp) <= 16 ? lpp : 0); };
+  st_init(phase_of(0), par);
+  __syncthreads();
+  // the levels unit by unit (each unit's ray and rows loaded once), their
+  // records through the staging pool, one phase per (unit round, level group)
+  for (int64_t it = 0; it < n_it; ++it) {
+    Unit q = unit_base(it);
+    for (int l = 0; l < 16;) {
+      const StPhase ph = phase_of(l);
+      const int np = l + (1 << lpp) <= 16 ? 1 << lpp : 1;
+      for (int j = 0; j < np; ++j, ++l) {
+        unit_grads(q, l);
+        level(q, l, ph);
+      }
+      __syncthreads();   // the phase's records are in the pool, its counts final
+      st_flush(ph);
+      // the next phase's bins (other parity), counts unchanged by the flush
+      const int ln = l < 16 ? l : (it + 1 < n_it ? 0 : 16);
+      if (ln < 16) st_init(phase_of(ln), par ^ 1);
+      __syncthreads();   // the pool is free again
+      par ^= 1;
+    }
+  }
+  // non-finite inputs (NaN / Inf in a grad or the point): one test per lane
+  if (__ballot(bad) != 0ull && lane == 0)
+    __hip_atomic_fetch_or(&g_hn_fault, kFaultNonFinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (k.tv_off[16] > 0) {
+    // The TV term's table gradient: one record per x-pair (x0, x0 + 1) of cube
+    // vertices of one (y, z) row, d TV_l / d e (tv_grad) scaled by g_tv[l] /
+    // cube, through the same region / overflow path as the render records
+    // (so the owner pass sums render + TV exactly and the table step stays fused)
+    const int total = k.tv_off[16], per = (total + (int)gridDim.x - 1) / (int)gridDim.x;
+    const int q0 = (int)blockIdx.x * per, q1 = q0 + per < total ? q0 + per : total;
+    const uint32_t T = (uint32_t)k.g.log2T;
+    for (int q = q0 + (int)threadIdx.x; q < q1; q += (int)blockDim.x) {
+      int l = 0;
+      while (l + 1 < k.tv.L && q >= k.tv_off[l + 1]) ++l;
+      const int c = k.tv.cube[l], n1 = c + 1, np = (n1 + 1) / 2, loc = q - k.tv_off[l];
+      const int ip = loc % np, j = (loc / np) % n1, kk = loc / (np * n1);
+      const uint32_t x0 = (uint32_t)(k.tv.mv[3 * l] + 2 * ip), y = (uint32_t)(k.tv.mv[3 * l + 1] + j),
+                     z = (uint32_t)(k.tv.mv[3 * l + 2] + kk);
+      const float scale = k.g_tv[l] / (float)c;
+      float v[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+      for (int f = 0; f < 2; ++f) v[f] = scale * tv_grad(k.tv, l, c, 2 * ip, j, kk, x0, y, z, f);
+      if (2 * ip + 1 <= c)
+#pragma unroll
+        for (int f = 0; f < 2; ++f) v[2 + f] = scale * tv_grad(k.tv, l, c, 2 * ip + 1, j, kk, x0 + 1u, y, z, f);
+      const float chk = (v[0] + v[1]) + (v[2] + v[3]);
+      if (!(fabsf(chk) <= 3.402823466e38f))
+        __hip_atomic_fetch_or(&g_hn_fault, kFaultNonFinite, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      const float vmax = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));
+      __hip_atomic_fetch_max(reinterpret_cast<uint32_t*>(&lvmx[l]), __float_as_uint(vmax), __ATOMIC_RELAXED,
+                             __HIP_MEMORY_SCOPE_WORKGROUP);
+      const RecSlot rs = rec_slot(bw, (uint32_t)l, T, x0, y * kPrimeY, z * kPrimeZ);
+      rec_store(bw, rs, v);
+    }
+  }
+  __syncthreads();
+  if (wave == 0) {   // lane = level: the max of its 64 lane slots
+    const int l = lane & 15, q = lane >> 4;
+    uint32_t m = 0u;
+    for (int j = 0; j < 16; ++j) m = max(m, lvmxl[l * 64 + 16 * q + j]);
+    __hip_atomic_fetch_max(reinterpret_cast<uint32_t*>(&lvmx[l]), m, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  }
+  __syncthreads();
+  uint32_t* cnt = book + nrec + blockIdx.x;
+  for (int i = threadIdx.x; i < k.nbins; i += blockDim.x) {
+    const uint32_t c = (uint32_t)bcnt[i];
+    cnt[(size_t)i * kBwdBlocks] = c;
+    if (c > bw.cap)   // spilled records of bin i (ovf_place_kernel's bucket sizes)
+      __hip_atomic_fetch_add(ob.per_bin + i, c - bw.cap, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  float* mxo = reinterpret_cast<float*>(book + nrec + (size_t)kBwdBlocks * k.nbins) + blockIdx.x;
+  if (threadIdx.x < 16) mxo[threadIdx.x * kBwdBlocks] = lvmx[threadIdx.x];
+  if (threadIdx.x == 0) {
+    const uint32_t n = lovf < bw.n_ovf ? lovf : bw.n_ovf;
+    ob.blk[blockIdx.x] = n;
+    if (n) __hip_atomic_fetch_add(ob.cnt, n, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  if (k.slab) {   // the dW slabs are complete (the MLP-backward kernel ran before this one)
+    float(*part)[64] = reinterpret_cast<float(*)[64]>(stv);   // the staging pool is free now
+    static_assert(kStPool * 20 >= sizeof(float) * kSlabGroups * 64 && 64 * kScWaves == 64 * kSlabGroups,
+                  "slab-reduce blocks inside the scatter blocks");
+    // the 292 slab blocks go to the scatter blocks as they finish (a counter
+    // reset by render_comp_bwd_kernel): the sums do not depend on who runs them
+    __shared__ int vb_sh;
+    for (;;) {
+      __syncthreads();   // part and vb_sh are free (the pool's last readers, or the previous combine)
+      if (threadIdx.x == 0)
+        vb_sh = (int)__hip_atomic_fetch_add(ob.slab_next, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __syncthreads();
+      const int vb = vb_sh;
+      if (vb >= kSlabVBlocks) break;
+      slab_reduce_block(k.slab, kBwdBlocks, k.dc, k.df, k.overwrite_mlp, vb, part, k.has_mstep ? k.mstep : nullptr,
+                        k.lmeta + 3);
+    }
+  }
+}
+
+// ---- the MLP backward over the work lists -----------------------------------
+// The coarse and fine tiles share one code path (the pass is a runtime flag:
+// weights, d raw offset, tile index and destination are selects), so the
+// kernel holds ONE copy of b1_tile: ~25 KB of code, under the 64 KB
+// instruction cache two CUs share.
+// A tile whose 32 samples all have d raw = 0 (raw2outputs' backward gives
+// exactly that to every sample with relu(sigma) = 0: alpha = 0, weight 0,
+// run_nerf_helpers.py:577-628) has an exactly zero MLP backward: zero
+// feature grads, and it adds 0 to every dW accumulator.  Such tiles are
+// skipped -- the same results (an accumulator plus exact zeros is unchanged)
+// for ~2/3 of the tiles of a trained scene (config 2: 57 % of the coarse and
+// 70 % of the fine tiles, scripts/zero_grad_frac.py).
+// Nothing is stored for them: the scatter kernel reads a sample's feature
+// grads only where its own d raw (or its coarse twin's) is nonzero.  The
+// weight ring is aligned to the tile period, so a skipped unit leaves it
+// ready for the next one.  The composite pre-pass marks the tiles with a
+// nonzero d raw (B1K::uflags), and the waves run lists of the marked tiles
+// (render_bwd_kernel): the same loop shape as over every tile (a per-tile
+// test inside the loop made the register allocator spill).
+// One MLP tile of two listed 16-sample groups (round 6): points 0-15 group
+// code ca, 16-31 group cb (codes ray << 4 | group; cb < 0: none, those lanes
+// run with d raw 0 and store nothing).  Each lane's ray gives its own SH
+// columns, and color_net.0's SH half is formed for both groups' rays at once
+// (column p of that product is point p's ray), kept in LDS per group.  The
+// two groups are often of different rays; every per-point input (features,
+// masks, d raw) is read at the point's own place in the ray's tiles and its
+// feature grads are written there, so the dW products and grads are those of
+// the dense form's tiles, grouped differently.
+HN_DEV void b1_groups(const B1K& k, int ca, int cb, bool fine, float* X, DW& dw, WRing& wr) {
+  const int lane = lane_id();
+  const int p = lane & 31, h = lane >> 5;
+  const bool none = p >= 16 && cb < 0;
+  const int code = p < 16 || cb < 0 ? ca : cb;
+  const int64_t ray = code >> 4;
+  const int i = 16 * (code & 15) + (p & 15);          // the point within its pass
+  float4 dr = *reinterpret_cast<const float4*>(k.draw + ((size_t)ray * (kSc + kSf) + (fine ? kSc : 0) + i) * 4);
+  if (none) dr = make_float4(0.f, 0.f, 0.f, 0.f);
+  const float* P = opaque_ptr(fine ? k.Pf : k.Pc);
+  C0Sh c0sh;
+  {
+    Ray r;
+    load_ray(k.rays, ray, r);
+    float sh8[8], shx8[8];
+    ray_sh(r, h, sh8, shx8);
+    const SP<2> sp = splitn<2>([&](int j) { return shx8[j]; });
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+      const u32x4 w = __builtin_bit_cast(u32x4, sp.p[q]);
+      put_quad(reinterpret_cast<char*>(X), kBC0in, q, p, 2 * h, w[0], w[1]);
+      put_quad(reinterpret_cast<char*>(X), kBC0in, q, p, 2 * h + 1, w[2], w[3]);
+    }
+    float* cl = X + kC0shF;
+#pragma unroll
+    for (int ob = 0; ob < 2; ++ob) {
+      const f32x16 v = gemm<R_F2S>(P, ob, zero16(), lane, [&](int s) { return sh8[s]; });
+      if ((p & 15) == 0)   // columns 0 and 16: the two groups' rays
+#pragma unroll
+        for (int g = 0; g < 4; ++g)
+          *reinterpret_cast<f32x4*>(cl + 64 * (p >> 4) + 32 * ob + row_of(4 * g, h)) =
+              f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+    }
+    lds_fence_wave();
+    c0sh.lds = cl + 64 * (p >> 4);
+  }
+  // the point's place in the saved tiles: tile (pass offset + i / 32), lane (i % 32) + 32 h
+  const int ctile = (fine ? kSc / 32 : 0) + (i >> 5), pl = (i & 31) + 32 * h;
+  const float* fb = k.feat + (size_t)ray * HN_RENDER_FEAT_PER_RAY;
+  f32x16 feat;
+  {
+    const f32x4* t = reinterpret_cast<const f32x4*>(fb + (size_t)ctile * 1024);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const f32x4 v = __builtin_nontemporal_load(t + 64 * c + pl);
+      feat[4 * c] = v.x; feat[4 * c + 1] = v.y; feat[4 * c + 2] = v.z; feat[4 * c + 3] = v.w;
+    }
+  }
+  uint32_t sm[3];
+  {
+    const uint32_t* t = reinterpret_cast<const uint32_t*>(fb + kTilesPerRay * 1024) + ctile * kMaskWordsPerTile;
+#pragma unroll
+    for (int j = 0; j < 3; ++j) sm[j] = __builtin_nontemporal_load(t + 64 * j + pl);
+  }
+  const f32x16 dfeat = b1_tile(P, wr, X, feat, c0sh, dr, dw, sm);
+  // this point's feature grads (the saved-feature tile order of both passes)
+  if (!none) {
+    f32x4* dst = fine ? reinterpret_cast<f32x4*>(k.dfeat_f + ((size_t)ray * (kSf / 32) + (i >> 5)) * 1024)
+                      : reinterpret_cast<f32x4*>(k.dfeat + (size_t)ray * kDcRay + (size_t)(i >> 5) * 1024);
+#pragma unroll
+    for (int c = 0; c < 4; ++c) {
+      const f32x4 v = f32x4{dfeat[4 * c], dfeat[4 * c + 1], dfeat[4 * c + 2], dfeat[4 * c + 3]};
+      __builtin_nontemporal_store(v, dst + 64 * c + pl);   // read once, by the scatter
+    }
+  }
+}
+
+// The binned scatter's overflow book starts empty (count, per bin, cursors,
+// the scatter blocks' slab-block counter): reset by workgroup 0 of the first
+// kernel of the backward.
+HN_DEV void zero_ovf_book(const B1K& k) {
+  const size_t nrec = bin_records(k.nbins, k.bin_cap, k.B);
+  uint32_t* o = ovf_book(reinterpret_cast<uint32_t*>(k.bins + 4 * nrec), nrec, k.nbins).cnt;
+  for (int i = threadIdx.x; i < 1 + 2 * k.nbins; i += blockDim.x) o[i] = 0u;
+  if (threadIdx.x == 0) o[1 + 3 * k.nbins] = 0u;   // the scatter kernel's slab-block counter (ob.slab_next)
+}
+
+// The backward's work lists (round 6), from the composite pre-pass's marks
+// (B1K::uflags; every group with dense_bwd): the coarse and the fine 16-sample
+// groups with a nonzero d raw (the MLP backward's) and the fine groups with
+// feature grads (the scatter's), each in ray order, as
+// codes (ray << 4 | 16-sample group); their lengths and the MLP waves' coarse / fine
+// split.  Workgroup w writes the codes of rays [w R, (w + 1) R): it counts
+// the marks of every earlier ray itself (a few loads per thread; no
+// workgroup waits for another), then takes 256 rays at a time, one per
+// thread, with a block-wide prefix of their counts.  (One 1,024-thread
+// workgroup for the whole batch took 14 us; computed redundantly by every
+// block of the kernels that use the lists it cost the MLP backward ~28 us.)
+constexpr int kListThreads = 256;
+constexpr int kListMaxBlocks = 64;
+HN_DEV int list_block_scan(int v, int* sh) {   // inclusive scan over the workgroup; sh: 4 ints of LDS
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  __syncthreads();   // sh free (its previous use is complete)
+  if (lane == 63) sh[wave] = v;
+  __syncthreads();
+  for (int q = 0; q < wave; ++q) v += sh[q];
+  return v;
+}
+HN_DEV int list_block_sum(int v, int* sh) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int o = 32; o >= 1; o >>= 1) v += __shfl_xor(v, o, 64);
+  __syncthreads();
+  if (lane == 0) sh[wave] = v;
+  __syncthreads();
+  return sh[0] + sh[1] + sh[2] + sh[3];
+}
+__global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k) {
+  static_assert(kListThreads == 256, "list_block_scan: 4 waves");
+  __shared__ int sh[3][4];
+  const int t = threadIdx.x;
+  // bits [coarse groups (4), -, fine groups (12), the scatter's groups (12)]
+  auto mword = [&](int64_t r) -> uint32_t {
+    return k.skip_zero ? *reinterpret_cast<const uint32_t*>(k.uflags + kMarkB * r) : 0xffffff0fu;
+  };
+  const int64_t R = (k.B + gridDim.x - 1) / gridDim.x;
+  const int64_t ra = (int64_t)blockIdx.x * R, rb = ra + R < k.B ? ra + R : k.B;
+  // the counts of the rays before this workgroup's range, and of all rays
+  int bc = 0, bf = 0, bs = 0, tc = 0, tf = 0, ts = 0;
+  for (int64_t r = t; r < k.B; r += kListThreads) {
+    const uint32_t w = mword(r);
+    const int c = __builtin_popcount(w & 15u), f = __builtin_popcount((w >> 8) & 0xfffu),
+              g = __builtin_popcount(w >> 20);
+    tc += c; tf += f; ts += g;
+    if (r < ra) { bc += c; bf += f; bs += g; }
+  }
+  int64_t xc = list_block_sum(bc, sh[0]), xf = list_block_sum(bf, sh[1]), xs = list_block_sum(bs, sh[2]);
+  const int64_t Nc = list_block_sum(tc, sh[0]), Nf = list_block_sum(tf, sh[1]), Ns = list_block_sum(ts, sh[2]);
+  int32_t* lc = k.lists;
+  int32_t* lf = lc + 4 * k.B;
+  int32_t* ls = lf + 12 * k.B;
+  for (int64_t r0 = ra; r0 < rb; r0 += kListThreads) {
+    const int64_t r = r0 + t;
+    const uint32_t w = r < rb ? mword(r) : 0u;
+    const int c = __builtin_popcount(w & 15u), f = __builtin_popcount((w >> 8) & 0xfffu),
+              g = __builtin_popcount(w >> 20);
+    const int ic = list_block_scan(c, sh[0]), jf = list_block_scan(f, sh[1]), ks = list_block_scan(g, sh[2]);
+    int64_t oc = xc + ic - c, of = xf + jf - f, os = xs + ks - g;
+    for (int i = 0; i < 4; ++i)
+      if ((w >> i) & 1u) lc[oc++] = (int32_t)(r << 4) | i;
+    for (int i = 0; i < 12; ++i)
+      if ((w >> (8 + i)) & 1u) lf[of++] = (int32_t)(r << 4) | i;
+    for (int i = 0; i < 12; ++i)
+      if ((w >> (20 + i)) & 1u) ls[os++] = (int32_t)(r << 4) | i;
+    xc += list_block_sum(c, sh[0]);
+    xf += list_block_sum(f, sh[1]);
+    xs += list_block_sum(g, sh[2]);
+  }
+  if (blockIdx.x == 0 && t == 0) {
+    const int G = kB1Waves * kBwdBlocks;
+    int gc = Nc > 0 ? G : 0;   // MLP waves on the coarse list, in proportion to the lists
+    if (Nc > 0 && Nf > 0) {
+      gc = (int)((2 * (int64_t)G * Nc + Nc + Nf) / (2 * (Nc + Nf)));
+      gc = gc < 1 ? 1 : (gc > G - 1 ? G - 1 : gc);
+    }
+    k.lmeta[0] = (int32_t)Nc;
+    k.lmeta[1] = (int32_t)Nf;
+    k.lmeta[2] = (int32_t)Ns;
+    k.lmeta[3] = gc;
+  }
+}
+
+// render_bwd_kernel<kSwVmcnt, kModeSplit>, the binned schedule's (only)
+// instantiation of the MLP-backward kernel (declared in hn_mlp_bwd.h): the MLP
+// backward over balanced tile lists (round 6).  The 16-sample groups with a
+// nonzero d raw (the composite pre-pass's marks; all of them with dense_bwd)
+// form two lists in ray order -- coarse groups, then fine groups,
+// render_lists_kernel -- and the kB1Waves x nb MLP waves g = 4 * block + wave
+// split them: the first gsplit waves the coarse list, the others the fine
+// list, in contiguous slices of equal length (gsplit in proportion to the two
+// lists).  Every wave then runs ~1/1024 of the work, whatever the scene leaves
+// nonzero; each wave keeps one net's dW.  A tile is two consecutive listed
+// groups (b1_groups).  A wave reads its codes 64 at a time (one vector load;
+// the tile loop takes them by readlane).
+// Then the block's waves g0 .. g0 + 3 -- the coarse net below gsplit, the
+// fine one from there -- sum each run of same-net waves into its first wave
+// (wave order, through `red`: the block's LDS), which alone stores slab g;
+// scatter_bins_kernel's slab reduction sums these leaders' slabs in g order:
+// deterministic (the split is a function of the marks alone).
+// The LDS (kB1LdsF floats at launch, laid out in hn_mlp_bwd.h): this schedule
+// uses the waves' operand images X, and all of it as `red`; the staged grid
+// sizes and the zeroed flags behind the images are not read here.
+template <>
+__global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
+void render_bwd_kernel<kSwVmcnt, kModeSplit>(B1K k) {
+  extern __shared__ f32x4 smem4[];
+  f32x4* const red = smem4;
+  float* smem = reinterpret_cast<float*>(smem4);
+  const int wave = threadIdx.x >> 6;
+  const int lane = threadIdx.x & 63;
+  float* X = smem + wave * kRRows * kXS;
+  float* gsl = smem + kB1GslF;
+  int* sync = reinterpret_cast<int*>(gsl + kGsLds);
+  stage_grid_sizes(k.g, gsl);
+  if (threadIdx.x < kSyncInts) sync[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t nb = gridDim.x, B = k.B;
+  const int blk = (int)blockIdx.x;
+  DW dw;
+  dw_zero(dw);
+  WRing wr;
+  const int wv = __builtin_amdgcn_readfirstlane(wave);    // wave-uniform (SGPR)
+  const int64_t Nc = __builtin_amdgcn_readfirstlane(k.lmeta[0]), Nf = __builtin_amdgcn_readfirstlane(k.lmeta[1]);
+  const int gc = __builtin_amdgcn_readfirstlane(k.lmeta[3]);
+  static_assert(kB1Waves == 4 && kSlabSlots == kB1Waves, "slab_reduce_block's run leaders: 4 waves per block");
+  const int G = kB1Waves * (int)nb, g_me = blk * kB1Waves + wv;
+  const bool fine = g_me >= gc;                            // wave-uniform
+  const int64_t N = fine ? Nf : Nc;
+  const int gi = fine ? g_me - gc : g_me, GG = fine ? G - gc : gc;
+  // slices of whole group pairs (a tile = two consecutive listed groups)
+  const int64_t NP = (N + 1) / 2;
+  const int64_t lo = GG ? 2 * ((int64_t)gi * NP / GG) : 0, hi2 = GG ? 2 * ((int64_t)(gi + 1) * NP / GG) : 0;
+  const int64_t hi = hi2 < N ? hi2 : N;
+  const int32_t* L = k.lists + (fine ? 4 * B : 0);
+  wring_prime(wr, fine ? k.Pf : k.Pc, lane);
+  for (int64_t c0 = lo; c0 < hi; c0 += 64) {   // lo even: pairs never straddle
+    const int cnt = (int)(hi - c0 < 64 ? hi - c0 : 64);
+    const int codes = lane < cnt ? L[c0 + lane] : -1;
+    for (int j = 0; j < cnt; j += 2) {
+      const int ca = __builtin_amdgcn_readlane(codes, j);
+      const int cb = j + 1 < cnt ? __builtin_amdgcn_readlane(codes, j + 1) : -1;
+      b1_groups(k, ca, cb, fine, X, dw, wr);
+    }
+  }
+  const int g0 = blk * kB1Waves;
+  for (int w = 1; w < kB1Waves; ++w) {
+    const bool w_leads = g0 + w == gc;                  // first fine wave of the block
+    int ldr = 0;                                        // the leader of wave w
+    if (g0 + w >= gc && g0 < gc) ldr = gc - g0;         // a fine wave behind the block's coarse ones
+    __syncthreads();
+    if (!w_leads && wv == w) dw_to_lds(dw, red, lane);
+    __syncthreads();
+    if (!w_leads && wv == ldr) dw_add_lds(dw, red, lane);
+  }
+  const bool leader = wv == 0 || g_me == gc;
+  if (leader) dw_flush(dw, k.slab + (size_t)g_me * W_END, lane);
+}
+
+// Owner pass of the binned scatter: workgroup b sums every record of bin b
+// (the regions of all kBwdBlocks producers, then the overflow records that
+// belong to it) and writes its slice of 2^shift entries of the table
+// gradient once: = (overwrite) or +=.  Every entry is written by exactly one
+// workgroup.
+//
+// The sums are exact integer sums.  On gfx950 ds_add_f32 runs ~20x slower than
+// integer LDS atomics (config 2: ~600 us for the bins' 71 M float adds, against
+// ~145 us with ds_add_u32 on the same addresses, ~125 us for the record loads
+// alone), and a bin's records are heavily duplicated (surfaces: e.g. 37.5 K
+// records on 2.9 K distinct entries at level 8), which defeats claiming
+// entries for plain read-modify-writes.  So each value is converted to a
+// 64-bit fixed-point integer in units of 2^(E - 40), E the exponent of the
+// bin's largest |value| (every value < 2^41 units, 2^20 of them < 2^61), and
+// added with ds_add_u64; the slice is converted back (one rounding to fp32).
+// Integer adds are associative, so the gradient is bitwise reproducible, and
+// every entry keeps full fp32 precision down to 2^-16 of the bin's largest
+// contribution (2^-40 absolute resolution below that).  Measured on recorded
+// config 2 bins (scripts/bin_stats.py): median relative error 1e-8 (fp32
+// sequential sums 6e-9 .. 2e-8); the worst entries, at |g| ~ 1e-17 with a bin
+// maximum ~ 5e-7, within 8e-3 -- where fp32 atomics cannot resolve them
+// either once a larger contribution has been added.
+constexpr int kBinThreads = 1024;
+constexpr int kSliceF4 = 4;   // float4s of a 2^13-entry slice per thread (2 x 2^13 floats / 4 / 1024)
+// The fused step's optimizer-state loads: 0 in the epilogue; 1 at kernel
+// start.  Measured on one box (config 2): 207.5 vs 214.8 / 204.5 us; loaded
+// after the setup 238 us, after the thread's last record fetch 217 us (64
+// VGPR spills): vmcnt waits are in order, so an earlier issue only moves the
+// wait to the first records.
+static_assert(kSliceF4 * kBinThreads * 4 >= (2 << 13), "bins are at most 2^13 entries (bin_geom)");
+constexpr int kBrDepth = 4;   // records per thread and fetch group (two groups in flight)
+constexpr int kBrChunks = 8192;   // table entries (16 KiB of LDS): bins of up to 512 K records
+
+
+// acc: [feature][entry] (entry e's accumulators 8 B apart per feature: a
+// wave's random entries spread over twice the LDS banks of [entry][feature])
+HN_DEV void bin_add(unsigned long long* acc, uint32_t se, const f32x4 v, uint32_t w, uint32_t sel,
+                    uint32_t tmask, float scale) {
+  const uint32_t e0 = w & 0x0fffffffu & sel;
+  const uint32_t e1 = e0 ^ (((1u << (w >> 28)) - 1u) & tmask);
+  const long long q[4] = {fx_of(v.x, scale), fx_of(v.y, scale), fx_of(v.z, scale), fx_of(v.w, scale)};
+  __hip_atomic_fetch_add(acc + e0, (unsigned long long)q[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_fetch_add(acc + se + e0, (unsigned long long)q[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_fetch_add(acc + e1, (unsigned long long)q[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __hip_atomic_fetch_add(acc + se + e1, (unsigned long long)q[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+}
+
+// Buckets the spilled records by bin.  Block j handles producer block j's
+// overflow list: it scans the per-bin spill counts (block 0 publishes the
+// first slot of each bin), counts its own records per bin in LDS, reserves one
+// range per touched bin with a single global atomic, and places the record
+// ids through LDS cursors (spilled records clump into few bins: per-record
+// global cursors serialise on them).  Returns at once when nothing spilled
+// (the usual case).
+constexpr int kPlaceThreads = 1024;   // 256 measured the same (r05: the launch, not its work)
+// The stepped NeRFSmall weights' MFMA copies (hn_render_bwd_args.repack):
+// extra workgroups of the placement launch, which runs after the scatter
+// kernel's slab reduction has stepped every weight (mlp_pack2_kernel's values)
+struct PackK {
+  hn_mlp c, f;
+  float* P;   // [2][G_END]: the workspace's packed copies (hn_render_fwd's Pc, Pf)
+};
+__global__ __launch_bounds__(kPlaceThreads) void ovf_place_kernel(BinR k, PackK pk) {
+  if (blockIdx.x >= kBwdBlocks) {
+    const int idx = (int)(blockIdx.x - kBwdBlocks) * kPlaceThreads + (int)threadIdx.x;
+    if (idx < 2 * G_END) pk.P[idx] = idx < G_END ? pack_value(pk.c, idx) : pack_value(pk.f, idx - G_END);
+    return;
+  }
+  __shared__ uint32_t cur[kScMaxBins], lc[kScMaxBins];
+  __shared__ uint32_t part[kPlaceThreads];
+  const size_t nrec = bin_records(k.nbins, k.cap, k.n_rays);
+  uint32_t* idx = const_cast<uint32_t*>(reinterpret_cast<const uint32_t*>(k.bins + 4 * nrec));
+  const OvfBook ob = ovf_book(idx, nrec, k.nbins);
+  if (*ob.cnt == 0u) return;
+  const uint32_t mine = ob.blk[blockIdx.x];
+  if (mine == 0u && blockIdx.x != 0) return;   // block 0 publishes `first`
+  const int per = (k.nbins + kPlaceThreads - 1) / kPlaceThreads, t = threadIdx.x;
+  uint32_t sum = 0;
+  for (int j = 0; j < per; ++j) {
+    const int bb = t * per + j;
+    if (bb < k.nbins) {
+      sum += ob.per_bin[bb];
+      lc[bb] = 0u;
+    }
+  }
+  part[t] = sum;
+  __syncthreads();
+  for (int d = 1; d < kPlaceThreads; d <<= 1) {   // inclusive scan of the thread sums
+    const uint32_t v = t >= d ? part[t - d] : 0u;
+    __syncthreads();
+    part[t] += v;
+    __syncthreads();
+  }
+  uint32_t run = part[t] - sum;
+  for (int j = 0; j < per; ++j) {
+    const int bb = t * per + j;
+    if (bb < k.nbins) {
+      cur[bb] = run;
+      if (blockIdx.x == 0) ob.first[bb] = run;
+      run += ob.per_bin[bb];
+    }
+  }
+  const size_t o0 = (size_t)blockIdx.x * ovf_per_block(k.n_rays);   // this list, relative to the overflow
+  const size_t l0 = (size_t)kBwdBlocks * k.nbins * k.cap + o0;   // first record of this list
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(k.bins);
+  auto bin_of = [&](uint32_t s) { return (words[rec_wofs(l0 + s, nrec)] & 0x0fffffffu) >> k.shift; };
+  for (uint32_t s = t; s < mine; s += kPlaceThreads)
+    __hip_atomic_fetch_add(lc + bin_of(s), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+  __syncthreads();
+  for (int j = 0; j < per; ++j) {
+    const int bb = t * per + j;
+    if (bb < k.nbins && lc[bb])
+      cur[bb] += __hip_atomic_fetch_add(ob.cur + bb, lc[bb], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+  __syncthreads();
+  for (uint32_t s = t; s < mine; s += kPlaceThreads) {
+    const uint32_t pos = __hip_atomic_fetch_add(cur + bin_of(s), 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    ob.ids[pos] = (uint32_t)(o0 + s);
+  }
+}
+
+// Records of the bin, flattened over the producers' regions: thread i takes
+// records i, i + 1024, ... (4 at a time, independent loads in flight) and
+// finds each one's region by binary search over the LDS prefix of the
+// regions' counts.
+__global__ __launch_bounds__(kBinThreads) void bin_reduce_kernel(BinR k) {
+  extern __shared__ f32x4 acc4[];
+  __shared__ uint32_t pre[kBwdBlocks + 1];
+  __shared__ uint32_t wsum[kBwdBlocks / 64], wmax[kBwdBlocks / 64];
+  unsigned long long* acc = reinterpret_cast<unsigned long long*>(acc4);
+  const int n4 = (2 << k.shift) / 2;   // f32x4 = 2 accumulators
+  const uint32_t b = (uint32_t)k.bin0 + blockIdx.x;
+  const size_t e0 = (size_t)b << (k.shift + 1);   // first float of the slice
+  const int nd4 = (2 << k.shift) / 4;             // float4s of the slice (<= 4 per thread)
+  // fused step on a coarse level: the row pairs no gradient can reach (their
+  // moments are zero, so the dense update leaves p, m, v bitwise unchanged)
+  // are neither loaded nor stored (table_live; T=19: levels 0-6)
+  const uint32_t* lw = nullptr;
+  if (k.fused && k.live && k.shift <= k.log2T && (int)(((uint32_t)b << k.shift) >> k.log2T) < k.live_levels)
+    lw = k.live + (((size_t)b << k.shift) >> 6);
+  auto live_at = [&](int i) { return lw == nullptr || ((lw[i >> 5] >> (i & 31)) & 1u) != 0u; };
+  for (int i = threadIdx.x; i < n4; i += kBinThreads) acc4[i] = f32x4{0.f, 0.f, 0.f, 0.f};
+  const size_t nrec = bin_records(k.nbins, k.cap, k.n_rays);
+  const uint32_t* words = reinterpret_cast<const uint32_t*>(k.bins);
+  const uint32_t* idx = reinterpret_cast<const uint32_t*>(k.bins + 4 * nrec);   // book base
+  const uint32_t* cnt = idx + nrec;
+  const float* mxs = reinterpret_cast<const float*>(cnt + (size_t)kBwdBlocks * k.nbins);   // [16][blocks]
+  const OvfBook obk = ovf_book(const_cast<uint32_t*>(idx), nrec, k.nbins);
+  const uint32_t n_ovf = *obk.cnt;
+  static_assert(kBwdBlocks == 256 && kBinThreads >= 256, "one count per thread of waves 0-3");
+  // levels of this bin: one, or all 16 when the whole table is one bin
+  const int lev0 = (int)(((uint32_t)b << k.shift) >> k.log2T);
+  const int nlev = k.shift > k.log2T ? 1 << (k.shift - k.log2T) : 1;
+  uint32_t n = 0;
+  float mx = 0.f;
+  if (threadIdx.x < kBwdBlocks) {
+    const uint32_t c = cnt[(size_t)b * kBwdBlocks + threadIdx.x];
+    n = c < (uint32_t)k.cap ? c : (uint32_t)k.cap;
+    for (int l = lev0; l < lev0 + nlev; ++l) mx = fmaxf(mx, mxs[l * kBwdBlocks + threadIdx.x]);
+  }
+  const uint32_t inc = (uint32_t)wave_incl_sum((double)n);   // exact: counts < 2^53
+  const float wmx = wave_max_f32(mx);
+  if (threadIdx.x < kBwdBlocks && (threadIdx.x & 63) == 63) {
+    wsum[threadIdx.x >> 6] = inc;
+    wmax[threadIdx.x >> 6] = wmx;
+  }
+  __syncthreads();
+  if (threadIdx.x < kBwdBlocks) {
+    uint32_t add = 0;
+    for (int q = 0; q < (int)(threadIdx.x >> 6); ++q) add += wsum[q];
+    pre[threadIdx.x + 1] = inc + add;
+  }
+  if (threadIdx.x == 0) pre[0] = 0;
+  // bin scale: every record value (overflow records included: the producers
+  // take every record) is below 2^(E+1) -> below 2^41 units
+  const float bmx = fmaxf(fmaxf(wmax[0], wmax[1]), fmaxf(wmax[2], wmax[3]));
+  const int E = ilogbf(bmx > 0.f ? bmx : 1.f);
+  // 2^(40 - E) as fp32 (E >= -126 + ... : the scale stays a normal float for
+  // every E in [-87, 127]; smaller maxima use 2^127, still < 2^41 units)
+  const int S = 40 - (E < -126 ? -126 : E);
+  const float scale = ldexpf(1.f, S > 127 ? 127 : S);
+  __syncthreads();
+  const uint32_t total = pre[kBwdBlocks];
+  const uint32_t sel = (1u << k.shift) - 1u, tmask = (1u << k.log2T) - 1u, se = 1u << k.shift;
+  // region of the first record of every 64-record chunk: a record's region is
+  // then a short forward walk from its chunk's (regions hold ~24-114 records)
+  // instead of an 8-step binary search
+  __shared__ uint16_t first_reg[kBrChunks];
+  const bool tab = ((total + 63) >> 6) <= (uint32_t)kBrChunks;   // uniform
+  if (tab) {
+    for (uint32_t c = threadIdx.x; c < ((total + 63) >> 6); c += kBinThreads) {
+      const uint32_t r = c << 6;
+      int lo = 0;
+#pragma unroll
+      for (int st = kBwdBlocks / 2; st >= 1; st >>= 1)
+        if (pre[lo + st] <= r) lo += st;
+      first_reg[c] = (uint16_t)lo;
+    }
+    __syncthreads();
+  }
+  const size_t bbase = (size_t)b * kBwdBlocks * k.cap;
+  // records r0 + q * 1024 (lane-consecutive: coalesced loads), each found in
+  // the regions' prefix from its 64-record chunk's first region (a binary
+  // search per record measured slower; both faster than one search per 4
+  // lane-consecutive records with their 64-B-strided loads); the next group
+  // of records is loaded before the current one is added
+  auto fetch = [&](uint32_t r0, f32x4 (&v)[kBrDepth], uint32_t (&w)[kBrDepth]) {
+#pragma unroll
+    for (int q = 0; q < kBrDepth; ++q) {
+      const uint32_t r = r0 + q * kBinThreads;
+      if (r < total) {
+        int lo = 0;   // largest p with pre[p] <= r
+        if (tab) {
+          lo = first_reg[r >> 6];
+          while (pre[lo + 1] <= r) ++lo;   // r < total = pre[kBwdBlocks]: stops by lo = 255
+        } else
+        {
+#pragma unroll
+          for (int st = kBwdBlocks / 2; st >= 1; st >>= 1)
+            if (pre[lo + st] <= r) lo += st;
+        }
+        const size_t rec = bbase + (size_t)lo * k.cap + (r - pre[lo]);
+        v[q] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(k.bins + rec_vofs(rec)));   // read once
+        w[q] = __builtin_nontemporal_load(words + rec_wofs(rec, nrec));
+      }
+    }
+  };
+  auto add = [&](uint32_t r0, const f32x4 (&v)[kBrDepth], const uint32_t (&w)[kBrDepth]) {
+#pragma unroll
+    for (int q = 0; q < kBrDepth; ++q)
+      if (r0 + q * kBinThreads < total) {
+        bin_add(acc, se, v[q], w[q], sel, tmask, scale);
+      }
+  };
+  f32x4 va[kBrDepth], vb[kBrDepth];
+  uint32_t wa[kBrDepth], wb[kBrDepth];
+  uint32_t r0 = threadIdx.x;
+  if (r0 < total) fetch(r0, va, wa);
+  for (; r0 < total; r0 += 2 * kBrDepth * kBinThreads) {
+    const uint32_t r1 = r0 + kBrDepth * kBinThreads;
+    if (r1 < total) fetch(r1, vb, wb);
+    add(r0, va, wa);
+    if (r1 >= total) break;
+    if (r1 + kBrDepth * kBinThreads < total) fetch(r1 + kBrDepth * kBinThreads, va, wa);
+    add(r1, vb, wb);
+  }
+  if (n_ovf) {   // this bin's spilled records (bucketed by ovf_place_kernel)
+    const size_t ob = (size_t)kBwdBlocks * k.nbins * k.cap;
+    const uint32_t lo = obk.first[b], hi = lo + obk.per_bin[b];
+    for (uint32_t s = lo + threadIdx.x; s < hi; s += kBinThreads) {
+      const uint32_t o = obk.ids[s];
+      bin_add(acc, se, *reinterpret_cast<const f32x4*>(k.bins + rec_vofs(ob + o)), words[rec_wofs(ob + o, nrec)],
+              sel, tmask, scale);
+    }
+  }
+  __syncthreads();
+  const double inv = 1.0 / (double)scale;
+  float4* dst = k.d_table ? reinterpret_cast<float4*>(k.d_table + e0) : nullptr;
+  if (k.fused && dst == nullptr) {
+    // fused step: the thread's live flags, then all of its p, m, v loads in
+    // flight at once (one HBM round trip instead of one per float4: the
+    // pass 90.5 -> 88.6 us on config 2)
+    bool lv[kSliceF4];
+#pragma unroll
+    for (int j = 0; j < kSliceF4; ++j) {
+      const int i = threadIdx.x + j * kBinThreads;
+      lv[j] = i < nd4 && live_at(i);
+    }
+    f32x4 p4[kSliceF4], m4[kSliceF4], v4[kSliceF4];
+#pragma unroll
+    for (int j = 0; j < kSliceF4; ++j) {
+      const int i = threadIdx.x + j * kBinThreads;
+      if (lv[j]) {
+        p4[j] = reinterpret_cast<const f32x4*>(k.step.p + e0)[i];
+        m4[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(k.step.m + e0) + i);
+        v4[j] = __builtin_nontemporal_load(reinterpret_cast<const f32x4*>(k.step.v + e0) + i);
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < kSliceF4; ++j) {
+      const int i = threadIdx.x + j * kBinThreads;
+      if (i >= nd4) break;
+      float4 a;
+      a.x = (float)((double)(long long)acc[2 * i] * inv);
+      a.y = (float)((double)(long long)acc[se + 2 * i] * inv);
+      a.z = (float)((double)(long long)acc[2 * i + 1] * inv);
+      a.w = (float)((double)(long long)acc[se + 2 * i + 1] * inv);
+      if (!lv[j]) {
+        if (a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f)
+          __hip_atomic_fetch_or(&g_hn_fault, kFaultDeadRow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        continue;
+      }
+      float4 p{p4[j][0], p4[j][1], p4[j][2], p4[j][3]}, m{m4[j][0], m4[j][1], m4[j][2], m4[j][3]},
+          v{v4[j][0], v4[j][1], v4[j][2], v4[j][3]};
+      radam_elem(k.step, p.x, a.x, m.x, v.x);
+      radam_elem(k.step, p.y, a.y, m.y, v.y);
+      radam_elem(k.step, p.z, a.z, m.z, v.z);
+      radam_elem(k.step, p.w, a.w, m.w, v.w);
+      __builtin_nontemporal_store(f32x4{m.x, m.y, m.z, m.w}, reinterpret_cast<f32x4*>(k.step.m + e0) + i);
+      __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, reinterpret_cast<f32x4*>(k.step.v + e0) + i);
+      if (k.step.mode != 0) reinterpret_cast<f32x4*>(k.step.p + e0)[i] = f32x4{p.x, p.y, p.z, p.w};
+    }
+    return;
+  }
+#pragma unroll
+  for (int j = 0; j < kSliceF4; ++j) {   // entries 2i, 2i + 1
+    const int i = threadIdx.x + j * kBinThreads;
+    if (i >= nd4) break;
+    float4 a;
+    a.x = (float)((double)(long long)acc[2 * i] * inv);
+    a.y = (float)((double)(long long)acc[se + 2 * i] * inv);
+    a.z = (float)((double)(long long)acc[2 * i + 1] * inv);
+    a.w = (float)((double)(long long)acc[se + 2 * i + 1] * inv);
+    if (dst) {
+      if (!k.overwrite) {
+        const float4 d = dst[i];
+        a.x = a.x + d.x; a.y = a.y + d.y; a.z = a.z + d.z; a.w = a.w + d.w;
+      }
+      dst[i] = a;
+    }
+    if (k.fused && !live_at(i)) {   // a dead pair: its gradient is a structural zero
+      if (a.x != 0.f || a.y != 0.f || a.z != 0.f || a.w != 0.f)
+        __hip_atomic_fetch_or(&g_hn_fault, kFaultDeadRow, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    } else if (k.fused) {   // RAdam on these 4 table elements (radam_kernel's update, same op forms)
+      f32x4* pp = reinterpret_cast<f32x4*>(k.step.p + e0) + i;
+      f32x4* pm = reinterpret_cast<f32x4*>(k.step.m + e0) + i;
+      f32x4* pv = reinterpret_cast<f32x4*>(k.step.v + e0) + i;
+      // m and v are nontemporal (next read by the next step's owner pass);
+      // p stays cached: the next forward gathers it (p nontemporal too
+      // measured the forward +10 us)
+      const f32x4 p4 = *pp, m4 = __builtin_nontemporal_load(pm), v4 = __builtin_nontemporal_load(pv);
+      float4 p{p4[0], p4[1], p4[2], p4[3]}, m{m4[0], m4[1], m4[2], m4[3]}, v{v4[0], v4[1], v4[2], v4[3]};
+      radam_elem(k.step, p.x, a.x, m.x, v.x);
+      radam_elem(k.step, p.y, a.y, m.y, v.y);
+      radam_elem(k.step, p.z, a.z, m.z, v.z);
+      radam_elem(k.step, p.w, a.w, m.w, v.w);
+      __builtin_nontemporal_store(f32x4{m.x, m.y, m.z, m.w}, pm);
+      __builtin_nontemporal_store(f32x4{v.x, v.y, v.z, v.w}, pv);
+      if (k.step.mode != 0) *pp = f32x4{p.x, p.y, p.z, p.w};
+    }
+  }
+}
+
+}  // namespace hn
+

@@ -30,28 +30,22 @@ namespace hn {
 //   split region (NS parts, hn_common.h): chunk c (k-steps 8c .. 8c+7) is NS
 //   groups, group NS*c + q = part q of those 8 values as bf16 (dword d of a
 //   lane = elements 2d, 2d+1).
-// HN_SPLIT_F: parts in the forward GEMMs (the forward pass and the backward's
+// kSplitF: parts in the forward GEMMs (the forward pass and the backward's
 // recompute, which therefore reproduce each other's activations bit for bit);
-// 3 makes them as accurate as f32.  HN_SPLIT_B: parts in the data-gradient and
+// 3 makes them as accurate as f32.  kSplitB: parts in the data-gradient and
 // weight-gradient GEMMs.  0 = f32 MFMA (an exact FMA chain).  color_net.2^T
 // (4 k-steps, 2 used) is always f32 (a 2-part split of its 3 rgb grads as one
 // K = 16 chunk measured no faster: 1.154-1.155 ms vs 1.159 ms per step, r03g).
-#ifndef HN_SPLIT_F
-#define HN_SPLIT_F 3
-#endif
-#ifndef HN_SPLIT_B
-#define HN_SPLIT_B 2
-#endif
+constexpr int kSplitF = 3;
+constexpr int kSplitB = 2;
 enum : int { R_F0, R_F1, R_F2G, R_F2S, R_F3, R_F4, R_B4, R_B3, R_B2G, R_B2S, R_B1, R_B0, R_N };
 //  F0 sigma_net.0  F1 sigma_net.1  F2G/F2S color_net.0 geo/sh  F3 color_net.1  F4 color_net.2
 //  B4 color_net.2^T  B3 color_net.1^T  B2G/B2S color_net.0^T geo/sh  B1 sigma_net.1^T  B0 sigma_net.0^T
 constexpr int kRegKS[R_N] = {16, 32, 8, 8, 32, 32, 4, 32, 32, 32, 8, 32};
 constexpr int kRegOB[R_N] = {2, 1, 2, 2, 2, 1, 2, 2, 1, 1, 2, 1};
-#ifndef HN_SPLIT_FC   // parts in the forward colour-net GEMMs (color_net.0-2)
-#define HN_SPLIT_FC HN_SPLIT_F
-#endif
+constexpr int kSplitFC = kSplitF;   // parts in the forward colour-net GEMMs (color_net.0-2)
 constexpr int reg_ns(int r) {
-  return kRegKS[r] % 8 ? 0 : (r < R_F2G ? HN_SPLIT_F : (r < R_B4 ? HN_SPLIT_FC : HN_SPLIT_B));
+  return kRegKS[r] % 8 ? 0 : (r < R_F2G ? kSplitF : (r < R_B4 ? kSplitFC : kSplitB));
 }
 constexpr int reg_gpo(int r) { return reg_ns(r) ? reg_ns(r) * kRegKS[r] / 8 : kRegKS[r] / 4; }   // groups per OB
 constexpr int reg_off(int r) {
@@ -121,16 +115,12 @@ HN_DEV void ring_fill(const float* P, float* slot, int off, int lane) {
   asm volatile("" : "+s"(so));
   const __amdgpu_buffer_rsrc_t rs =
       __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(opaque_ptr(P)), (short)0, 0x7fffffff, 0x00020000);
-#ifndef HN_DIAG_RING2
-#define HN_DIAG_RING2 0
-#endif
 #pragma unroll
-  for (int q = 0; q < (HN_DIAG_RING2 ? 2 : 3); ++q)   // HN_DIAG_RING2: timing diagnostic only (stale third part)
+  for (int q = 0; q < 3; ++q)
     __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void*)(slot + 256 * q), 16,
                                              lane * 16, so + 1024 * q, 0, 0);
 }
 HN_DEV void fwd_ring_start(const float* P, float* slot, int lane) {
-  if (HN_DIAG_RING2) *reinterpret_cast<f32x4*>(slot + 512 + 4 * lane) = f32x4{0.f, 0.f, 0.f, 0.f};
   ring_fill(P, slot, fwd_chunk_off(kFwdSeq[0]), lane);
 }
 template <int R, typename BF, typename Src>

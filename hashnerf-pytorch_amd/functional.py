@@ -318,9 +318,15 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     workspace, for a next render_fwd(wsb=st.wsb, weights_packed=True)."""
     B = st.rays.shape[0]
     dev = st.rays.device
-    if getattr(st, "skip_dead", False) and st.cfg.dense_bwd:
-        raise ValueError("hashnerf_amd.render_bwd: the forward ran with skip_dead_color (features of tiles "
-                         "without density not stored); the backward needs cfg.dense_bwd = 0")
+    if getattr(st, "skip_dead", False):
+        # only the binned dense_bwd = 0 backward runs lists of the tiles that were stored
+        if st.cfg.dense_bwd:
+            raise ValueError("hashnerf_amd.render_bwd: the forward ran with skip_dead_color (features of tiles "
+                             "without density not stored); the backward needs cfg.dense_bwd = 0")
+        if L.lib().hn_render_scatter_mode(st.cfg, B) != 2:
+            raise ValueError("hashnerf_amd.render_bwd: the forward ran with skip_dead_color (features of tiles "
+                             "without density not stored); the float-atomic backward this configuration runs "
+                             "(hn_render_scatter_mode != 2) loads every tile")
     a = L.HnRenderBwdArgs()
     a.n_rays = B
     a.coarse = L.make_mlp(st.ws[:5])

@@ -212,9 +212,12 @@ typedef struct hn_render_fwd_args {
                                net: raw_c / raw_f rgb of those samples are written as 0 (rgb, depth,
                                acc, the entropies and every gradient unchanged), and such fine
                                tiles' features and ReLU masks are not stored in `feat` (no d raw of
-                               theirs is nonzero, so a dense_bwd = 0 backward never reads them; a
-                               dense_bwd = 1 backward of this state is invalid).  0 = every sample's
-                               raw rgb computed (the reference's `raw` output), every tile stored */
+                               theirs is nonzero, so the binned dense_bwd = 0 backward, which runs
+                               lists of the nonzero groups, never reads them).  Only that backward
+                               may follow: hn_render_scatter_mode == 2 and dense_bwd = 0.  The
+                               float-atomic schedule and a dense_bwd = 1 backward load every tile,
+                               so either one of this state is invalid.  0 = every sample's raw
+                               rgb computed (the reference's `raw` output), every tile stored */
 } hn_render_fwd_args;
 
 typedef struct hn_render_bwd_args {

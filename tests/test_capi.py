@@ -126,6 +126,25 @@ def test_bins_and_deferred_owner_validation_without_gpu(hn):
         assert HF.render_bins(cfg, 4096) == want, (T, HF.render_bins(cfg, 4096))
         cfg_a = HF.make_render_cfg(emb.grid(), True, False, True, scatter="atomic")
         assert HF.render_bins(cfg_a, 4096) == (0, 0)
+    # the host plan (schedule, bins, workspace bytes) as the library before the
+    # schedules were separated computed it: (T, finest, n_rays, scatter, bin_cap)
+    plan = (((14, 64, 64, "binned", 0), (2, (32, 13), 186440376)),
+            ((14, 8192, 64, "binned", 0), (1, (0, 0), 39308576)),      # cell index does not fit a bin
+            ((12, 8192, 64, "binned", 0), (2, (8, 13), 162822552)),
+            ((19, 512, 64, "binned", 0), (2, (1024, 13), 1099729208)),
+            ((23, 512, 64, "binned", 0), (1, (0, 0), 39308576)),       # T > 22
+            ((19, 512, 64, "atomic", 0), (1, (0, 0), 39308576)),
+            ((19, 512, 4096, "binned", 192), (2, (1024, 13), 2431626296)),
+            ((19, 512, 0, "binned", 0), (2, (1024, 13), 1097362488)),
+            ((22, 1024, 8192, "auto", 0), (2, (8192, 13), 10844912696)),
+            ((14, 8192, 64, "auto", 0), (1, (0, 0), 39308576)),
+            ((14, 64, 0, "atomic", 0), (1, (0, 0), 38514720)))
+    for (T, finest, n, scatter, cap), want in plan:
+        emb = hn.HashEmbedder(box, log2_hashmap_size=T, finest_resolution=finest)
+        cfg = HF.make_render_cfg(emb.grid(), True, False, True, scatter=scatter)
+        cfg.bin_cap = cap
+        got = (lib.hn_render_scatter_mode(cfg, n), HF.render_bins(cfg, n), lib.hn_render_workspace_bytes(cfg, n))
+        assert got == want, ((T, finest, n, scatter, cap), got)
     shift = C.c_int32(-1)
     assert lib.hn_render_bins(None, 4096, C.byref(shift)) == 0
     emb = hn.HashEmbedder(box, log2_hashmap_size=19, finest_resolution=512)
@@ -230,4 +249,9 @@ def test_render_bwd_refuses_dense_after_skipping_forward(hn):
     st.skip_dead = True
     st.cfg.dense_bwd = 1
     with pytest.raises(ValueError, match="dense_bwd"):
+        HF.render_bwd(st, {}, None, [])
+    # the float-atomic schedule loads every fine tile too: refused as well
+    st.cfg = HF.make_render_cfg(emb.grid(), True, False, True, scatter="atomic")
+    assert st.cfg.dense_bwd == 0 and hn._lib.lib().hn_render_scatter_mode(st.cfg, 4) == 1
+    with pytest.raises(ValueError, match="float-atomic"):
         HF.render_bwd(st, {}, None, [])

@@ -462,3 +462,54 @@ def test_zero_gradient_skip_bitwise(hn):
         rel = float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
         assert rel <= 1e-5, f"gradient {k}: skipped vs dense relative {rel:.3e}"
         assert torch.equal(b, c), f"gradient {k}: not repeatable"
+
+
+def test_trainer_atomic_schedule_keeps_every_tile(hn, monkeypatch):
+    """a forward with skip_dead_color stores no features for fine
+    tiles without density, which only the binned backward's work lists never
+    read.  At T=14 with finest resolution 8192 the cell index does not fit a
+    bin, so hn_render_scatter_mode is 1 and the trainer runs the float-atomic
+    schedule, which loads every tile: its forward must store them all.  The
+    default trainer then hands the backward a state with skip_dead False, one
+    step leaves every gradient and parameter finite, and it agrees with a
+    dense_bwd trainer of the same seed within test_binned_matches_atomic's
+    bounds for float-atomic sums (table 1e-6, NeRFSmall tensors 1e-4)."""
+    from hashnerf_pytorch_amd import functional as HF
+    from hashnerf_pytorch_amd.train import SyntheticBlender, Trainer, default_args
+    data = SyntheticBlender(32, 32, 2, DEV, seed=0)
+    states = []
+    real_bwd = HF.render_bwd
+
+    def spy(st, *a, **kw):
+        states.append(st)
+        return real_bwd(st, *a, **kw)
+
+    monkeypatch.setattr(HF, "render_bwd", spy)
+
+    def rel(a, b):
+        return float((a.double() - b.double()).norm() / b.double().norm().clamp_min(1e-30))
+
+    res = {}
+    for dense in (False, True):
+        args = default_args(N_rand=64, log2_hashmap_size=14, finest_res=8192, tv_loss_weight=0.0)
+        tr = Trainer(args, data, DEV, seed=3)
+        tr.dense_bwd = dense
+        torch.manual_seed(11)
+        tr.step()
+        torch.cuda.synchronize()
+        HF.L.check_device_faults()
+        assert HF.L.lib().hn_render_scatter_mode(tr._cfg, 64) == 1 and not tr._binned
+        assert bool(tr._cfg.dense_bwd) == dense
+        ws = tr.kw_train["network_fn"].weights() + tr.kw_train["network_fine"].weights()
+        res[dense] = ([tr.embed_fn.table.grad.detach().clone()] + [p.grad.detach().clone() for p in ws],
+                      [tr.embed_fn.table.detach().clone()] + [p.detach().clone() for p in ws])
+    assert len(states) == 2 and not states[0].skip_dead and not states[1].skip_dead
+    for grads, params in res.values():
+        for x in grads + params:
+            assert bool(torch.isfinite(x).all())
+    assert torch.count_nonzero(res[False][0][0]) > 0
+    for part in (0, 1):
+        a, b = res[False][part], res[True][part]
+        print("table rel", rel(a[0], b[0]), "NeRFSmall rel", [rel(x, y) for x, y in zip(a[1:], b[1:])])
+        assert rel(a[0], b[0]) <= 1e-6
+        assert max(rel(x, y) for x, y in zip(a[1:], b[1:])) <= 1e-4

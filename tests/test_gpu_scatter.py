@@ -404,6 +404,32 @@ def test_tv_records_match_tv_bwd(hn):
     assert _rel(d_b - _bwd(HF, emb, ws, st, grads)[0], tv_only) <= 1e-5
 
 
+def test_tv_large_cube_added_after_binned_backward(hn):
+    """A TV cube past the records' bound (51 > kTvRecMaxCube = 50) cannot join
+    the binned scatter's records: hn_render_bwd then adds the TV term to
+    d_table with hn_tv_bwd's float atomics after the owner pass
+    (hashnerf_amd.h, hn_render_bwd_args.tv), on the binned schedule as on the
+    atomic one.  Equal to the render backward plus a standalone hn_tv_bwd, to
+    fp32 summation order (test_tv_records_match_tv_bwd's bounds)."""
+    HF, emb, mc, mf, ws, rays, t_rand, u, target, st, grads = _state(hn, 1024, 19, 23, "binned")
+    assert HF.L.lib().hn_render_scatter_mode(st.cfg, 1024) == 2
+    mvd, cubes, g_tv = _tv_inputs(HF, emb)
+    cubes = list(cubes)
+    cubes[15] = 51
+    base, _ = _bwd(HF, emb, ws, st, grads)
+    d_a = base.clone()
+    HF.tv_bwd(emb.table.detach(), mvd, cubes, emb.log2_hashmap_size, g_tv, d_a)
+    d_b = torch.zeros_like(emb.table)
+    HF.render_bwd(st, grads, d_b, HF.zeros_like_all(ws), tv=(mvd, cubes, g_tv))
+    torch.cuda.synchronize()
+    HF.L.check_device_faults()
+    tv_only = d_a - base
+    assert torch.count_nonzero(tv_only) > 0
+    print("rel", _rel(d_b, d_a), "tv-only rel", _rel(d_b - base, tv_only))
+    assert _rel(d_b, d_a) <= 1e-6, _rel(d_b, d_a)
+    assert _rel(d_b - base, tv_only) <= 1e-5
+
+
 @pytest.mark.parametrize("T", [14, 19])
 def test_tv_only_records_bitwise(hn, T):
     """hn_render_bwd with no rays and a TV term (ABI 14; a data-parallel rank
