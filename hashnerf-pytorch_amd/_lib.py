@@ -60,7 +60,8 @@ class HnRenderFwdArgs(C.Structure):
                 ("rgb", _P), ("depth", _P), ("acc", _P), ("sparsity", _P),
                 ("rgb0", _P), ("depth0", _P), ("acc0", _P), ("sparsity0", _P),
                 ("z_std", _P), ("z_coarse", _P), ("z_fine", _P), ("raw_c", _P), ("raw_f", _P),
-                ("fine_src", _P), ("feat", _P), ("weights_packed", C.c_int32), ("skip_dead_color", C.c_int32)]
+                ("fine_src", _P), ("feat", _P), ("weights_packed", C.c_int32), ("skip_dead_color", C.c_int32),
+                ("loss", C.POINTER(HnRenderLoss))]
 
 
 class HnRadamTensor(C.Structure):
@@ -81,7 +82,7 @@ class HnRenderBwdArgs(C.Structure):
                 ("table_step", C.POINTER(HnRadamTensor)), ("tv", C.c_void_p), ("g_tv", _P),
                 ("table_live", _P), ("table_live_levels", C.c_int32), ("owner_defer", C.c_int32),
                 ("loss", C.POINTER(HnRenderLoss)), ("mlp_step", C.POINTER(HnRadamTensor)),
-                ("repack", C.c_int32)]
+                ("repack", C.c_int32), ("prepass_done", C.c_int32)]
 
 
 class HnTvArgs(C.Structure):
@@ -185,7 +186,8 @@ def check(status: int, what: str):
 FAULT_BITS = {1: "ring slot wait", 2: "ring drain (tiles left unscattered)", 4: "coarse-grad flag wait",
               8: "dW buffer wait", 16: "binned-scatter overflow records exhausted",
               32: "non-finite (NaN / Inf) feature gradient or sample point in the binned scatter",
-              64: "gradient on a table row pair the live mask marks dead (fused table step)"}
+              64: "gradient on a table row pair the live mask marks dead (fused table step)",
+              128: "prepass_done without a training forward of these rays on this workspace"}
 
 
 def check_device_faults(clear: bool = True):

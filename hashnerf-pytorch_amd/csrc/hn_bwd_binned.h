@@ -779,6 +779,15 @@ HN_DEV void zero_ovf_book(const B1K& k) {
 // block of the kernels that use the lists it cost the MLP backward ~28 us.)
 constexpr int kListThreads = 256;
 constexpr int kListMaxBlocks = 64;
+static_assert(kListMaxBlocks + 1 <= (int)kStampCount, "the stamp's low byte counts the lists kernel's workgroups");
+// What one workgroup's atomic add saw of the forward's stamp: valid for
+// n_rays when it is that stamp plus the adds of at most the other workgroups;
+// the workgroup that saw all the others' clears it.
+HN_DEV bool stamp_check(unsigned long long* stamp, unsigned long long seen, int64_t n_rays, int n_groups) {
+  const bool ok = (seen & ~kStampCount) == stamp_word(n_rays) && (int)(seen & kStampCount) < n_groups;
+  if (ok && (int)(seen & kStampCount) == n_groups - 1) *stamp = 0ull;
+  return ok;
+}
 HN_DEV int list_block_scan(int v, int* sh) {   // inclusive scan over the workgroup; sh: 4 ints of LDS
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
 #pragma unroll
@@ -801,16 +810,44 @@ HN_DEV int list_block_sum(int v, int* sh) {
   __syncthreads();
   return sh[0] + sh[1] + sh[2] + sh[3];
 }
-__global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k) {
+// stamp (hn_render_bwd_args.prepass_done; NULL otherwise): the training
+// forward wrote d raw and the marks, no pre-pass ran, and this is the
+// backward's first kernel.  One extra workgroup, dispatched first, takes the
+// pre-pass's two side jobs (the overflow book, the loss value).  Every
+// workgroup checks the forward's stamp with one atomic add (asked for at
+// once, looked at after the counting loop, which reads marks inside the
+// workspace whatever they hold); without a stamp for these n_rays the kernel
+// raises kFaultPrepass, leaves the lists alone and reports them empty.  The
+// workgroup whose add came last clears the stamp: one backward per training
+// forward.
+__global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k, unsigned long long* stamp) {
   static_assert(kListThreads == 256, "list_block_scan: 4 waves");
   __shared__ int sh[3][4];
+  __shared__ int stamp_ok;
   const int t = threadIdx.x;
+  int bx = (int)blockIdx.x, nbx = (int)gridDim.x;
+  unsigned long long seen = 0ull;
+  if (stamp) {
+    if (t == 0) seen = __hip_atomic_fetch_add(stamp, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (bx == 0) {
+      zero_ovf_book(k);   // binned scatter: no overflow records yet
+      loss_fwd_block<kListThreads>(k.lrgb, k.lrgb0, k.ltarget, k.lsp, k.lsp0, k.B, k.ltv, k.n_tv, k.lworld,
+                                   k.lsparse_w, k.ltv_w, k.lout);
+      if (t == 0 && !stamp_check(stamp, seen, k.B, nbx)) {
+        raise_fault(kFaultPrepass);
+        for (int i = 0; i < 4; ++i) k.lmeta[i] = 0;   // no units: the kernels behind this one touch no ray
+      }
+      return;
+    }
+    --bx;
+    --nbx;
+  }
   // bits [coarse groups (4), -, fine groups (12), the scatter's groups (12)]
   auto mword = [&](int64_t r) -> uint32_t {
     return k.skip_zero ? *reinterpret_cast<const uint32_t*>(k.uflags + kMarkB * r) : 0xffffff0fu;
   };
-  const int64_t R = (k.B + gridDim.x - 1) / gridDim.x;
-  const int64_t ra = (int64_t)blockIdx.x * R, rb = ra + R < k.B ? ra + R : k.B;
+  const int64_t R = (k.B + nbx - 1) / nbx;
+  const int64_t ra = (int64_t)bx * R, rb = ra + R < k.B ? ra + R : k.B;
   // the counts of the rays before this workgroup's range, and of all rays
   int bc = 0, bf = 0, bs = 0, tc = 0, tf = 0, ts = 0;
   for (int64_t r = t; r < k.B; r += kListThreads) {
@@ -820,7 +857,9 @@ __global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k) {
     tc += c; tf += f; ts += g;
     if (r < ra) { bc += c; bf += f; bs += g; }
   }
+  if (stamp && t == 0) stamp_ok = stamp_check(stamp, seen, k.B, nbx + 1) ? 1 : 0;
   int64_t xc = list_block_sum(bc, sh[0]), xf = list_block_sum(bf, sh[1]), xs = list_block_sum(bs, sh[2]);
+  if (stamp && !stamp_ok) return;   // (written before list_block_sum's barriers)
   const int64_t Nc = list_block_sum(tc, sh[0]), Nf = list_block_sum(tf, sh[1]), Ns = list_block_sum(ts, sh[2]);
   int32_t* lc = k.lists;
   int32_t* lf = lc + 4 * k.B;
@@ -842,7 +881,7 @@ __global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k) {
     xf += list_block_sum(f, sh[1]);
     xs += list_block_sum(g, sh[2]);
   }
-  if (blockIdx.x == 0 && t == 0) {
+  if (bx == 0 && t == 0) {
     const int G = kB1Waves * kBwdBlocks;
     int gc = Nc > 0 ? G : 0;   // MLP waves on the coarse list, in proportion to the lists
     if (Nc > 0 && Nf > 0) {

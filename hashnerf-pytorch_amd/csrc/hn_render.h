@@ -131,14 +131,12 @@ HN_DEV void composite_totals(const CompSamples<N>& cs, CompTotals& t) {
 HN_DEV float ent_logit(float p) { return logf(p < kEps32 ? kEps32 : (p > 1.f - kEps32 ? 1.f - kEps32 : p)); }
 HN_DEV bool ent_inside(float p) { return p >= kEps32 && p <= 1.f - kEps32; }
 
-// Forward.  Writes per-sample weights to wout (may be null).
+// Forward outputs from a ray's samples and totals (composite_fwd's second
+// half; a caller that also takes the backward shares cs and t with
+// composite_bwd_raw).  Writes per-sample weights to wout (may be null).
 template <int N>
-HN_DEV void composite_fwd(const float* raw, const float* z, const float* noise, int S, float dnorm,
-                          bool white, float* wout, CompOut& o, int lane) {
-  CompSamples<N> cs;
-  composite_samples<N>(raw, z, noise, S, dnorm, cs, lane);
-  CompTotals t;
-  composite_totals<N>(cs, t);
+HN_DEV void composite_fwd_out(const CompSamples<N>& cs, const CompTotals& t, bool white, float* wout, CompOut& o,
+                              int lane) {
   double ent = 0;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
@@ -158,6 +156,17 @@ HN_DEV void composite_fwd(const float* raw, const float* z, const float* noise, 
   o.entropy = -(float)(ent + (double)entS);
 }
 
+// Forward.  Writes per-sample weights to wout (may be null).
+template <int N>
+HN_DEV void composite_fwd(const float* raw, const float* z, const float* noise, int S, float dnorm,
+                          bool white, float* wout, CompOut& o, int lane) {
+  CompSamples<N> cs;
+  composite_samples<N>(raw, z, noise, S, dnorm, cs, lane);
+  CompTotals t;
+  composite_totals<N>(cs, t);
+  composite_fwd_out<N>(cs, t, white, wout, o, lane);
+}
+
 // Upstream gradients of one ray.  has_* false => that output has no grad.
 struct CompGrad {
   float rgb[3];
@@ -165,17 +174,13 @@ struct CompGrad {
   bool has_rgb, has_acc, has_depth, has_entropy;
 };
 
-// Backward w.r.t. raw: writes draw[j] (float4, may alias raw: each lane reads
-// its own samples before writing them).  gw: per-sample grad of weights or
-// null; graw: external grad of raw (added) or null.
+// Backward w.r.t. raw from a ray's samples and totals (composite_bwd's second
+// half): writes draw[j] (float4; may alias the raw the samples were read
+// from).  gw: per-sample grad of weights or null; graw: external grad of raw
+// (added) or null.
 template <int N>
-HN_DEV void composite_bwd(const float* raw, const float* z, const float* noise, int S, float dnorm,
-                          bool white, const CompGrad& g, const float* gw, const float* graw,
-                          float* draw, int lane) {
-  CompSamples<N> cs;
-  composite_samples<N>(raw, z, noise, S, dnorm, cs, lane);
-  CompTotals t;
-  composite_totals<N>(cs, t);
+HN_DEV void composite_bwd_raw(const CompSamples<N>& cs, const CompTotals& t, bool white, const CompGrad& g,
+                              const float* gw, const float* graw, float* draw, int lane) {
   // entropy: dH/dw_j = (g_j - g_S) / Q with g_k = -(log(clamp p_k) + inside_k)
   const float pS = t.qS / t.Q;
   const float gS = -(ent_logit(pS) + (ent_inside(pS) ? 1.f : 0.f));
@@ -223,6 +228,19 @@ HN_DEV void composite_bwd(const float* raw, const float* z, const float* noise, 
     }
     *reinterpret_cast<float4*>(draw + 4 * j) = d;
   }
+}
+
+// Backward w.r.t. raw: writes draw[j] (float4, may alias raw: each lane reads
+// its own samples before writing them).
+template <int N>
+HN_DEV void composite_bwd(const float* raw, const float* z, const float* noise, int S, float dnorm,
+                          bool white, const CompGrad& g, const float* gw, const float* graw,
+                          float* draw, int lane) {
+  CompSamples<N> cs;
+  composite_samples<N>(raw, z, noise, S, dnorm, cs, lane);
+  CompTotals t;
+  composite_totals<N>(cs, t);
+  composite_bwd_raw<N>(cs, t, white, g, gw, graw, draw, lane);
 }
 
 // torch.sum over a contiguous fp32 row on the CPU (ATen SumKernel.cpp

@@ -1,6 +1,8 @@
 // hn_render.hip -- fused render_rays (run_nerf_helpers.py:464-574) for one
 // training ray batch: the C entry points hn_render_fwd / hn_render_bwd, the
-// pre-pass kernel of both backward schedules, and the host side.  One
+// pre-pass kernel of both backward schedules (not launched by the binned one
+// after a training forward that did its work, hn_render_fwd_args.loss), and
+// the host side.  One
 // translation unit; the device code is in the headers (each says what it holds).
 #include "hn_render_args.h"   // kernel arguments, rays, feature cache, shared helpers
 #include "hn_render_fwd.h"    // render_fwd_kernel
@@ -58,13 +60,8 @@ __global__ __launch_bounds__(256) void render_comp_bwd_kernel(B1K k) {
     const float* gdep = fine ? k.g_depth : k.g_depth0;
     const float* gent = fine ? k.g_sparsity : k.g_sparsity0;
     if (k.lout) {   // the training loss's gradients (hn_loss_bwd_elem's op forms, g_loss = 1)
-      const float* x = fine ? k.lrgb : k.lrgb0;
-      g.has_rgb = g.has_entropy = true;
-      g.has_acc = g.has_depth = false;
-#pragma unroll
-      for (int c = 0; c < 3; ++c) g.rgb[c] = k.lgm * (2.f * (x[3 * ray + c] - k.ltarget[3 * ray + c]));
-      g.acc = g.depth = 0.f;
-      g.entropy = k.lsparse;
+      const float* x = (fine ? k.lrgb : k.lrgb0) + 3 * ray;
+      loss_comp_grad(g, k.lgm, k.lsparse, x[0], x[1], x[2], k.ltarget + 3 * ray);
     } else {
       g.has_rgb = grgb != nullptr;
       g.has_acc = gacc != nullptr;
@@ -85,39 +82,17 @@ __global__ __launch_bounds__(256) void render_comp_bwd_kernel(B1K k) {
     else
       composite_bwd<kSc / 64>(rawb, zb, noise, S, r.dnorm, k.white != 0, g, nullptr, graw, rawb, lane);
     lds_fence_wave();
-    uint32_t nzu = 0u;   // bit t: a sample of 16-sample group t has a nonzero d raw (the MLP's)
-    for (int j = lane; j < S; j += 64) {
-      const float4 d = *reinterpret_cast<const float4*>(rawb + 4 * j);
-      *reinterpret_cast<float4*>(dst + 4 * j) = d;
-      const uint64_t b = __ballot(draw_nonzero(d));
-#pragma unroll
-      for (int q = 0; q < 4; ++q) nzu |= (((b >> (16 * q)) & 0xffffull) != 0ull ? 1u : 0u) << (4 * (j >> 6) + q);
-    }
+    // bit t: a sample of 16-sample group t has a nonzero d raw (the MLP's)
+    const uint32_t nzu = draw_store_marks(rawb, dst, S, lane);
     if (lane == 0 && !fine) k.uflags[kMarkB * ray] = (uint8_t)nzu;   // byte 0: the coarse groups
     nzf = nzu;
-    if (!fine) cmask[wave >> 1] = __ballot(draw_nonzero(*reinterpret_cast<const float4*>(rawb + 4 * lane)));
+    if (!fine) cmask[wave >> 1] = coarse_nonzero_mask(rawb, lane);
   }
   __syncthreads();
   if (active && fine) {
-    // the scatter's marks: bit t = a sample of fine tile t, or its coarse twin
-    // (the same point, fine_src < 64), has a nonzero d raw -- the tile has
-    // feature grads to scatter (scatter_bins_kernel's lists)
-    const unsigned long long cm = cmask[wave >> 1];
-    uint32_t su = 0u;   // bit t: fine 16-sample group t has feature grads to scatter
-    for (int j = lane; j < kSf; j += 64) {
-      const int src = k.fine_src[ray * kSf + j];
-      const bool nz = draw_nonzero(*reinterpret_cast<const float4*>(rawb + 4 * j)) ||
-                      (src < kSc && ((cm >> src) & 1ull) != 0ull);
-      const uint64_t b = __ballot(nz);
-#pragma unroll
-      for (int q = 0; q < 4; ++q) su |= (((b >> (16 * q)) & 0xffffull) != 0ull ? 1u : 0u) << (4 * (j >> 6) + q);
-    }
-    if (lane == 0) {   // bits 8-19: the fine MLP groups, 20-31: the scatter's groups
-      const uint32_t v = nzf | (su << 12);
-      k.uflags[kMarkB * ray + 1] = (uint8_t)v;
-      k.uflags[kMarkB * ray + 2] = (uint8_t)(v >> 8);
-      k.uflags[kMarkB * ray + 3] = (uint8_t)(v >> 16);
-    }
+    // the scatter's marks (bits 20-31), beside the fine MLP groups (8-19)
+    const uint32_t su = scatter_marks(rawb, k.fine_src + ray * kSf, cmask[wave >> 1], lane);
+    if (lane == 0) store_fine_marks(k.uflags, ray, nzf, su);
   }
 }
 
@@ -209,7 +184,8 @@ static int bwd_mode(const hn_render_cfg* c, int64_t n_rays) {
 // the staging pool).
 // Workspace (floats): packed coarse + fine weights | dW slabs [256][4][9344] |
 // coarse-pass feature grads [n][64][32] | d raw [n][256][4] | unit marks
-// [n][4] u8, the lists' counts [8], the lists [(4 + 12 + 12) n] | binned: fine
+// [n][4] u8, the lists' counts [8] (words 4-7: the training forward's stamp,
+// ws_stamp), the lists [(4 + 12 + 12) n] | binned: fine
 // feature grads [n][6][1024] (dfeat_f) and the records (bins; bin_geom).
 struct BwdPlan {
   int mode;          // kModeSplit (binned) or kModeAtomic
@@ -233,6 +209,29 @@ static BwdPlan bwd_plan(const hn_render_cfg* cfg, int64_t n_rays) {
   }
   return p;
 }
+// Where the composite backward's results live in the workspace (the layout
+// above), for the pre-pass and for the training forward that replaces it.
+struct WsDraw {
+  float *slab, *dfeat, *draw;
+  uint8_t* uflags;
+  int32_t* lmeta;
+};
+static WsDraw ws_draw(void* workspace, int64_t n_rays) {
+  WsDraw w;
+  w.slab = (float*)workspace + 2 * (size_t)G_END;
+  w.dfeat = w.slab + (size_t)kBwdBlocks * kSlabSlots * W_END;
+  w.draw = w.dfeat + (size_t)n_rays * kDcRay;
+  w.uflags = reinterpret_cast<uint8_t*>(w.draw + (size_t)n_rays * (kSc + kSf) * 4);
+  // the work lists' counts (and the training forward's stamp) and the lists, after the marks
+  w.lmeta = reinterpret_cast<int32_t*>(w.uflags + kMarkB * (size_t)n_rays);
+  return w;
+}
+
+// The training forward's stamp: the 8-byte aligned word within lmeta[4..7]
+static unsigned long long* ws_stamp(int32_t* lmeta) {
+  return reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(lmeta + kStampAt) + 7) & ~(uintptr_t)7);
+}
+
 // scatter_bins_kernel's dynamic LDS fits beside its static LDS, read once
 // from the code object (a constant here would silently go stale
 // if the static arrays grow).  Checked before anything is queued.
@@ -337,7 +336,13 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
       !a->fine_src)
     return HN_E_NULL;
   if (!workspace) return HN_E_NULL;
-  if (ws_bytes < hn_render_workspace_bytes(cfg, a->n_rays)) return HN_E_WORKSPACE;
+  const BwdPlan plan = bwd_plan(cfg, a->n_rays);
+  if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
+  if (a->loss) {   // the composite backward of the training loss done here (only target, world, sparse_w read)
+    if (!a->loss->target) return HN_E_NULL;
+    if (!(a->loss->world > 0.f)) return HN_E_SHAPE;
+    if (plan.mode != kModeSplit) return HN_E_SHAPE;   // only the binned backward can skip its pre-pass
+  }
   hipStream_t s = (hipStream_t)stream;
   float* Pc = (float*)workspace;
   float* Pf = Pc + G_END;
@@ -362,8 +367,24 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
   // 633 -> 682 us)
   k.feat_nt = cfg->grid.log2_hashmap_size > 20;
   k.skip_dead = a->skip_dead_color != 0;
+  k.ltarget = nullptr;
+  k.lgm = k.lsparse = 0.f;
+  k.draw = nullptr;
+  k.uflags = nullptr;
+  k.stamp = nullptr;
   const unsigned blocks = (unsigned)((a->n_rays + kFwdBlockWaves - 1) / kFwdBlockWaves);
-  hipLaunchKernelGGL(render_fwd_kernel, dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+  if (a->loss) {
+    const WsDraw w = ws_draw(workspace, a->n_rays);
+    k.ltarget = a->loss->target;
+    k.lgm = (1.f / a->loss->world) / (float)(3 * a->n_rays);   // hn_render_bwd's factors (g_loss = 1)
+    k.lsparse = 1.f * a->loss->sparse_w;
+    k.draw = w.draw;
+    k.uflags = w.uflags;
+    k.stamp = ws_stamp(w.lmeta);
+    hipLaunchKernelGGL(render_fwd_kernel<true>, dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+  } else {
+    hipLaunchKernelGGL(render_fwd_kernel<false>, dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+  }
   return hip_status(hipGetLastError());
 }
 
@@ -449,13 +470,18 @@ static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a
 static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a, const BwdPlan& plan, const B1K& k,
                           const hn_tv_args* tv, const TvK& tvk, void* workspace, hipStream_t s) {
   int32_t st;
-  hipLaunchKernelGGL(render_comp_bwd_kernel,
-                     dim3((unsigned)((2 * a->n_rays + kFwdWaves - 1) / kFwdWaves + (k.lout ? 1 : 0))),
-                     dim3(64 * kFwdWaves), 0, s, k);
-  // the backward's work lists (from the pre-pass's marks)
+  // prepass_done: the training forward left d raw and the marks; the lists
+  // kernel checks its stamp and takes the pre-pass's side jobs in one extra
+  // workgroup (dense_bwd = 1 runs the same kernel, listing every group)
+  const int prepass = a->prepass_done ? 1 : 0;
+  if (!prepass)
+    hipLaunchKernelGGL(render_comp_bwd_kernel,
+                       dim3((unsigned)((2 * a->n_rays + kFwdWaves - 1) / kFwdWaves + (k.lout ? 1 : 0))),
+                       dim3(64 * kFwdWaves), 0, s, k);
+  // the backward's work lists (from the marks)
   const int64_t nlb = (a->n_rays + kListThreads - 1) / kListThreads;
-  hipLaunchKernelGGL(render_lists_kernel, dim3((unsigned)(nlb < kListMaxBlocks ? nlb : kListMaxBlocks)),
-                     dim3(kListThreads), 0, s, k);
+  hipLaunchKernelGGL(render_lists_kernel, dim3((unsigned)(nlb < kListMaxBlocks ? nlb : kListMaxBlocks) + prepass),
+                     dim3(kListThreads), 0, s, k, prepass ? ws_stamp(k.lmeta) : nullptr);
   if ((st = hip_status(hipGetLastError()))) return st;
   hipLaunchKernelGGL((render_bwd_kernel<kSwVmcnt, kModeSplit>), dim3(kBwdBlocks), dim3(64 * kB1Waves),
                      (size_t)kB1LdsF * sizeof(float), s, k);
@@ -559,6 +585,9 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
       return HN_E_NULL;
     if (L.n_tv < 0 || !(L.world > 0.f)) return HN_E_SHAPE;
   }
+  // d raw and marks from the training forward: the binned schedule with the
+  // loss formed here, no explicit upstream gradients
+  if (a->prepass_done && (!binned || !a->loss || a->g_raw_f || a->g_rgb || a->g_rgb0)) return HN_E_SHAPE;
   // the fused table step lives in the binned scatter's owner pass
   if (a->table_step && !binned) return HN_E_SHAPE;
   if ((st = check_table_step(cfg, a))) return st;
@@ -609,12 +638,12 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   k.g_rgb = a->g_rgb; k.g_depth = a->g_depth; k.g_acc = a->g_acc; k.g_sparsity = a->g_sparsity;
   k.g_rgb0 = a->g_rgb0; k.g_depth0 = a->g_depth0; k.g_acc0 = a->g_acc0;
   k.g_sparsity0 = a->g_sparsity0; k.g_raw_f = a->g_raw_f;
-  k.slab = Pf + G_END;
-  k.dfeat = k.slab + (size_t)kBwdBlocks * kSlabSlots * W_END;
-  k.draw = k.dfeat + (size_t)a->n_rays * kDcRay;
-  k.uflags = reinterpret_cast<uint8_t*>(k.draw + (size_t)a->n_rays * (kSc + kSf) * 4);
-  // the work lists' counts and the lists, after the marks
-  k.lmeta = reinterpret_cast<int32_t*>(k.uflags + kMarkB * (size_t)a->n_rays);
+  const WsDraw w = ws_draw(workspace, a->n_rays);
+  k.slab = w.slab;
+  k.dfeat = w.dfeat;
+  k.draw = w.draw;
+  k.uflags = w.uflags;
+  k.lmeta = w.lmeta;
   k.lists = k.lmeta + 8;
   k.ltarget = k.lrgb = k.lrgb0 = k.lsp = k.lsp0 = k.ltv = nullptr;
   k.n_tv = 0;

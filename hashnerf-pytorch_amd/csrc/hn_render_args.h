@@ -40,6 +40,14 @@ struct RenderK {
   float* feat;    // [B][8 tiles][1024] saved features or NULL
   int feat_nt;    // saved features stored nontemporally (tables past the MALL)
   int skip_dead;  // hn_render_fwd_args.skip_dead_color
+  // render_fwd_kernel<true> (hn_render_fwd_args.loss): the training loss's
+  // composite backward done by the ray's own forward wave -- hn_loss_bwd's
+  // factors (g = 1) and the workspace's d raw, marks and stamp (B1K's)
+  const float* ltarget;
+  float lgm, lsparse;
+  float* draw;
+  uint8_t* uflags;
+  unsigned long long* stamp;
 };
 
 
@@ -265,6 +273,9 @@ HN_DEV void voxel_cw(const GridArgs& g, const float* gsl, const float pt[3], con
 __device__ int g_hn_fault;
 enum : int { kFaultSlot = 1, kFaultDrain = 2, kFaultCoarse = 4, kFaultDwBuf = 8 };
 enum : int { kFaultBins = 16, kFaultNonFinite = 32, kFaultDeadRow = 64 };
+// kFaultPrepass: hn_render_bwd_args.prepass_done without a training forward
+// of the same n_rays on this workspace since the last backward (no stamp).
+enum : int { kFaultPrepass = 128 };
 HN_DEV void raise_fault(int bit) {
   if (lane_id() == 0) __hip_atomic_fetch_or(&g_hn_fault, bit, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
@@ -277,6 +288,77 @@ constexpr int kMarkB = 4;   // unit-mark bytes per ray (B1K::uflags)
 // skip_zero = 0).
 HN_DEV bool draw_nonzero(const float4& d) {
   return ((__float_as_uint(d.x) | __float_as_uint(d.y) | __float_as_uint(d.z) | __float_as_uint(d.w)) << 1) != 0u;
+}
+
+// ---- the composite backward of one ray's pass, shared by the pre-pass
+// (render_comp_bwd_kernel) and the training forward (render_fwd_kernel<true>)
+// The training loss's upstream gradients of a pass with outputs rgb
+// (hn_loss_bwd_elem's op forms, g_loss = 1): lgm 2 (rgb - target), lsparse.
+HN_DEV void loss_comp_grad(CompGrad& g, float lgm, float lsparse, float r0, float r1, float r2,
+                           const float* __restrict__ target) {
+  g.has_rgb = g.has_entropy = true;
+  g.has_acc = g.has_depth = false;
+  g.rgb[0] = lgm * (2.f * (r0 - target[0]));
+  g.rgb[1] = lgm * (2.f * (r1 - target[1]));
+  g.rgb[2] = lgm * (2.f * (r2 - target[2]));
+  g.acc = g.depth = 0.f;
+  g.entropy = lsparse;
+}
+// Bits 4 i .. 4 i + 3: the 16-lane quarters of a wave ballot that have a set bit
+// (the 16-sample groups of samples 64 i .. 64 i + 63).
+HN_DEV uint32_t group_bits(uint64_t b, int i) {
+  uint32_t v = 0u;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) v |= (((b >> (16 * q)) & 0xffffull) != 0ull ? 1u : 0u) << (4 * i + q);
+  return v;
+}
+// A pass's d raw (S samples in LDS) stored to the workspace; returns its MLP
+// marks: bit t = a sample of 16-sample group t has a nonzero d raw.
+HN_DEV uint32_t draw_store_marks(const float* rawb, float* __restrict__ dst, int S, int lane) {
+  uint32_t nzu = 0u;
+  for (int j = lane; j < S; j += 64) {
+    const float4 d = *reinterpret_cast<const float4*>(rawb + 4 * j);
+    *reinterpret_cast<float4*>(dst + 4 * j) = d;
+    nzu |= group_bits(__ballot(draw_nonzero(d)), j >> 6);
+  }
+  return nzu;
+}
+// The coarse pass's nonzero-sample mask (bit s: coarse sample s).
+HN_DEV unsigned long long coarse_nonzero_mask(const float* rawb, int lane) {
+  return __ballot(draw_nonzero(*reinterpret_cast<const float4*>(rawb + 4 * lane)));
+}
+// The scatter's marks of a ray: bit t = a sample of fine group t, or its
+// coarse twin (the same point, fine_src < 64; cm = coarse_nonzero_mask), has a
+// nonzero d raw -- the group has feature grads to scatter.
+HN_DEV uint32_t scatter_marks(const float* rawb, const uint8_t* __restrict__ fine_src, unsigned long long cm,
+                              int lane) {
+  uint32_t su = 0u;
+  for (int j = lane; j < kSf; j += 64) {
+    const int src = fine_src[j];
+    const bool nz = draw_nonzero(*reinterpret_cast<const float4*>(rawb + 4 * j)) ||
+                    (src < kSc && ((cm >> src) & 1ull) != 0ull);
+    su |= group_bits(__ballot(nz), j >> 6);
+  }
+  return su;
+}
+// Mark bytes 1-3 of a ray (bits 8-19: the fine MLP groups nzf, 20-31: the
+// scatter's groups su); byte 0 is the coarse pass's MLP groups.
+HN_DEV void store_fine_marks(uint8_t* __restrict__ uflags, int64_t ray, uint32_t nzf, uint32_t su) {
+  const uint32_t v = nzf | (su << 12);
+  uflags[kMarkB * ray + 1] = (uint8_t)v;
+  uflags[kMarkB * ray + 2] = (uint8_t)(v >> 8);
+  uflags[kMarkB * ray + 3] = (uint8_t)(v >> 16);
+}
+
+// The training forward's stamp in the workspace: one 64-bit word in the spare
+// words behind the lists' counts (B1K::lmeta[4..7]), n_rays << 32 |
+// kStampToken; the token's low byte counts the workgroups of the backward's
+// first kernel, which check it with one atomic add each -- the last one
+// clears it (render_lists_kernel; hn_render_bwd_args.prepass_done).
+constexpr int kStampAt = 4;
+constexpr unsigned long long kStampToken = 0x70726500ull, kStampCount = 0xffull;
+HN_DEV constexpr unsigned long long stamp_word(int64_t n_rays) {
+  return ((unsigned long long)n_rays << 32) | kStampToken;
 }
 
 // Arguments of scatter_bins_kernel (binned schedule).

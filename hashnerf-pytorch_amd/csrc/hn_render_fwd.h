@@ -37,6 +37,37 @@ constexpr int kFwdWavesPerSimd = 4;
 constexpr int kFwdBlockWaves = kFwdWaves;
 
 
+// One pass's composite.  kLoss: then also the training loss's composite
+// backward from the same samples and totals (composite_bwd's two halves, so
+// the d raw are the pre-pass's bit for bit), written over raw in LDS.
+template <bool kLoss, int N>
+HN_DEV void composite_pass(const RenderK& k, int64_t ray, float* rawb, const float* z, const float* noise, int S,
+                           float dnorm, float* wout, CompOut& o, int lane) {
+  if constexpr (!kLoss) {
+    composite_fwd<N>(rawb, z, noise, S, dnorm, k.white != 0, wout, o, lane);
+  } else {
+    // (the ray's target colour asked for ahead of the composite that hides its latency)
+    const float target[3] = {k.ltarget[3 * ray], k.ltarget[3 * ray + 1], k.ltarget[3 * ray + 2]};
+    CompSamples<N> cs;
+    composite_samples<N>(rawb, z, noise, S, dnorm, cs, lane);
+    CompTotals t;
+    composite_totals<N>(cs, t);
+    composite_fwd_out<N>(cs, t, k.white != 0, wout, o, lane);
+    CompGrad g;
+    loss_comp_grad(g, k.lgm, k.lsparse, o.rgb[0], o.rgb[1], o.rgb[2], target);
+    composite_bwd_raw<N>(cs, t, k.white != 0, g, nullptr, nullptr, rawb, lane);
+    lds_fence_wave();
+  }
+}
+
+// kLoss (hn_render_fwd_args.loss, the trainer's step): the wave also runs the
+// composite backward of its ray's two passes on the raw / z it holds in LDS
+// -- what render_comp_bwd_kernel would read back from memory, and the samples
+// and totals its composite forward has just formed -- and writes the ray's d
+// raw and marks into the backward's workspace (the binned schedule then
+// launches no pre-pass).  Both passes' composites sit outside the tile loops.
+// kLoss = false compiles to the forward without any of it.
+template <bool kLoss>
 __global__ __launch_bounds__(64 * kFwdBlockWaves)
 __attribute__((amdgpu_waves_per_eu(kFwdWavesPerSimd, kFwdWavesPerSimd)))
 void render_fwd_kernel(RenderK k) {
@@ -61,6 +92,10 @@ void render_fwd_kernel(RenderK k) {
   // against 229.4 us -- the forward's per-XCD work is balanced already)
   const int64_t grp = nb % 8 == 0 ? (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8 : blockIdx.x;
   const int64_t ray = grp * kFwdBlockWaves + wave;
+  if constexpr (kLoss) {
+    // the stamp render_lists_kernel checks: d raw and marks of these n_rays follow
+    if (blockIdx.x == 0 && threadIdx.x == 0) *k.stamp = stamp_word(k.B);
+  }
   if (ray >= k.B) return;
   float* L = smem + wave * kFLds;
   float* zc = L + kFZc;
@@ -122,14 +157,22 @@ void render_fwd_kernel(RenderK k) {
   }
   lds_fence_wave();
   CompOut co;
-  composite_fwd<1>(rawb, zc, k.noise_c ? k.noise_c + ray * kSc : nullptr, kSc, r.dnorm, k.white != 0,
-                   wts, co, lane);
+  composite_pass<kLoss, kSc / 64>(k, ray, rawb, zc, k.noise_c ? k.noise_c + ray * kSc : nullptr, kSc, r.dnorm, wts,
+                                  co, lane);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) k.rgb0[3 * ray + c] = co.rgb[c];
     k.depth0[ray] = co.depth;
     k.acc0[ray] = co.acc;
     k.sparsity0[ray] = co.entropy;
+  }
+  // kLoss: rawb now holds the coarse pass's d raw (it is free until the fine
+  // tiles; wts stays intact for sample_pdf_wave)
+  unsigned long long cmask = 0ull;   // the coarse samples with a nonzero d raw
+  if constexpr (kLoss) {
+    const uint32_t nzu = draw_store_marks(rawb, k.draw + (size_t)ray * (kSc + kSf) * 4, kSc, lane);
+    if (lane == 0) k.uflags[kMarkB * ray] = (uint8_t)nzu;   // byte 0: the coarse groups
+    cmask = coarse_nonzero_mask(rawb, lane);
   }
 
   // ---- importance sampling (:547-551) ----
@@ -157,6 +200,13 @@ void render_fwd_kernel(RenderK k) {
   lds_fence_wave();
   asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the coarse ring's last (unused) fill has landed
   fwd_ring_start(k.Pf, fring[wave], lane);
+  // kLoss: the samples' coarse origins kept in LDS for the marks (zsrc is free
+  // after the merge), read beside the first fine tile's own look at them
+  uint8_t* srcl = reinterpret_cast<uint8_t*>(zsrc);
+  if constexpr (kLoss) {
+    for (int i = lane; i < kSf; i += 64) srcl[i] = k.fine_src[ray * kSf + i];
+    lds_fence_wave();
+  }
   for (int tau = 0; tau < kSf / 32; ++tau) {
     const float* P = opaque_ptr(k.Pf);
     const int q = 32 * tau + p;
@@ -171,7 +221,8 @@ void render_fwd_kernel(RenderK k) {
     // importance samples as 4 full tiles first and loading every fine tile's
     // features back from the cache (a third fewer encode instructions) measured
     // slower: 0.301 ms, the waves then run their MLP tiles in step (r04j).
-    const int src = k.feat ? (int)k.fine_src[ray * kSf + q] : 255;
+    // (kLoss: from the LDS copy -- no global round trip ahead of each tile's gathers)
+    const int src = !k.feat ? 255 : kLoss ? (int)srcl[q] : (int)k.fine_src[ray * kSf + q];
     if (src >= kSc) {
       HN_FWD_PRIO_HI();
       encode_tile(k.g, gsl, k.table, pt, h, feat);
@@ -207,14 +258,19 @@ void render_fwd_kernel(RenderK k) {
   }
   lds_fence_wave();
   CompOut fo;
-  composite_fwd<3>(rawb, zs, k.noise_f ? k.noise_f + ray * kSf : nullptr, kSf, r.dnorm, k.white != 0,
-                   nullptr, fo, lane);
+  composite_pass<kLoss, kSf / 64>(k, ray, rawb, zs, k.noise_f ? k.noise_f + ray * kSf : nullptr, kSf, r.dnorm,
+                                  nullptr, fo, lane);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) k.rgb[3 * ray + c] = fo.rgb[c];
     k.depth[ray] = fo.depth;
     k.acc[ray] = fo.acc;
     k.sparsity[ray] = fo.entropy;
+  }
+  if constexpr (kLoss) {   // the fine pass's d raw and the ray's marks
+    const uint32_t nzf = draw_store_marks(rawb, k.draw + ((size_t)ray * (kSc + kSf) + kSc) * 4, kSf, lane);
+    const uint32_t su = scatter_marks(rawb, srcl, cmask, lane);
+    if (lane == 0) store_fine_marks(k.uflags, ray, nzf, su);
   }
 }
 

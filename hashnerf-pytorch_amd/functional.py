@@ -9,6 +9,7 @@ from __future__ import annotations
 
 import ctypes as C
 import os
+import weakref
 from typing import Optional, Sequence
 
 import torch
@@ -218,11 +219,17 @@ class RenderState:
     outputs, coarse origin of each fine sample, hash features, the workspace
     holding the packed weights)."""
     __slots__ = ("cfg", "rays", "noise_c", "noise_f", "table", "ws", "z_c", "z_f", "raw_c", "raw_f",
-                 "fine_src", "feat", "wsb", "nbytes", "bwd_args", "skip_dead")
+                 "fine_src", "feat", "wsb", "nbytes", "bwd_args", "skip_dead", "prepass_done", "__weakref__")
+
+
+# workspace address -> the state of the last forward that ran the composite
+# backward into it (render_fwd(loss=...)): one workspace holds one ray batch's
+# d raw, so a later such forward on it invalidates the earlier state's
+_PREPASS_ON_WS = {}
 
 
 def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_feat, wsb=None,
-               weights_packed=False, skip_dead_color=False):
+               weights_packed=False, skip_dead_color=False, loss=None):
     """hn_render_fwd (run_nerf_helpers.py:464-574, forward).  Returns the
     output dict and a RenderState (None when keep_feat is False).  wsb: the
     caller's workspace (uint8, >= workspace_bytes; default a fresh one);
@@ -232,7 +239,13 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     rgb, depth, acc, the entropies and every gradient unchanged, the raw rgb
     of those samples written as 0 -- and such fine tiles' features are not
     stored: the backward must then run with cfg.dense_bwd = 0 (render_bwd
-    refuses dense_bwd = 1 on such a state)."""
+    refuses dense_bwd = 1 on such a state).
+    loss = dict(target [B, 3], world, sparse_w) (the trainer's step, binned
+    scatter only): each ray's forward wave also runs the composite backward
+    of the training loss on the raw / z it still holds, and leaves d raw and
+    the work marks in the workspace; the state's one render_bwd then takes
+    the same loss with prepass_done=True and launches no pre-pass (bitwise
+    the same gradients; every output here is unchanged)."""
     L.require_device(rays, t_vals, t_rand, u, noise_c, noise_f, table, *ws)
     rays, t_vals, t_rand, u, noise_c, noise_f = (L.contig(t) for t in (rays, t_vals, t_rand, u,
                                                                       noise_c, noise_f))
@@ -268,6 +281,18 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
         nbytes = wsb.numel() * wsb.element_size()
     a.weights_packed = 1 if weights_packed else 0
     a.skip_dead_color = 1 if skip_dead_color else 0
+    la = None
+    if loss is not None:
+        if not keep_feat:
+            raise ValueError("hashnerf_amd.render_fwd: loss= is for a forward whose backward follows (keep_feat)")
+        target = L.contig(loss["target"])
+        L.require_device(target)
+        if tuple(target.shape) != (B, 3):
+            raise ValueError(f"hashnerf_amd.render_fwd: loss target must be [{B}, 3]")
+        la = L.HnRenderLoss()
+        la.target = target.data_ptr()
+        la.world, la.sparse_w = float(loss["world"]), float(loss["sparse_w"])
+        a.loss = C.pointer(la)
     t0 = TIMER.begin("render_fwd")
     L.check(L.lib().hn_render_fwd(cfg, a, L.ptr(wsb), nbytes, L.stream(dev)), "render_fwd")
     TIMER.end("render_fwd", t0)
@@ -281,12 +306,17 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
         st.fine_src, st.feat, st.wsb, st.nbytes = fine_src, feat, wsb, nbytes
         st.bwd_args = None
         st.skip_dead = bool(skip_dead_color)
+        # what the backward's loss must repeat (None: no composite backward ran here)
+        st.prepass_done = None if la is None else (target.data_ptr(), float(loss["world"]),
+                                                   float(loss["sparse_w"]))
+        if la is not None:
+            _PREPASS_ON_WS[wsb.data_ptr()] = weakref.ref(st)
     return out, st
 
 
 def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = False, table_step=None,
                overwrite_mlp: bool = False, tv=None, table_live=None, owner_defer: bool = False, loss=None,
-               mlp_step=None, repack: bool = False):
+               mlp_step=None, repack: bool = False, prepass_done: bool = False):
     """hn_render_bwd: accumulates (+=) d loss / d table into d_table (or
     writes it, overwrite=True: d_table need not be zeroed) and the ten
     NeRFSmall weight gradients into dws (coarse 5, fine 5, +=; written with
@@ -315,9 +345,29 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     RAdam.take_step for st.ws's tensors, applied where each weight's final
     gradient is formed (the slab reduction; dws is still written); with
     repack=True the stepped weights' packed copies are then written into the
-    workspace, for a next render_fwd(wsb=st.wsb, weights_packed=True)."""
+    workspace, for a next render_fwd(wsb=st.wsb, weights_packed=True).
+    prepass_done=True (with loss): st's render_fwd ran with this loss, so d
+    raw and the marks are in the workspace and no composite pre-pass is
+    launched.  Refused here when st's forward did not (or another such
+    forward has used the workspace since, or a backward has consumed it);
+    the library checks the forward's stamp on the device as well (fault
+    bit 128)."""
     B = st.rays.shape[0]
     dev = st.rays.device
+    if prepass_done:
+        done = getattr(st, "prepass_done", None)
+        if done is None:
+            raise ValueError("hashnerf_amd.render_bwd: prepass_done needs a render_fwd(loss=...) of this state "
+                             "that no backward has used yet")
+        if loss is None:
+            raise ValueError("hashnerf_amd.render_bwd: prepass_done needs the forward's loss")
+        owner = _PREPASS_ON_WS.get(st.wsb.data_ptr())
+        if owner is None or owner() is not st:
+            raise ValueError("hashnerf_amd.render_bwd: prepass_done, but another render_fwd(loss=...) has used "
+                             "this workspace since this state's")
+        if done != (L.contig(loss["target"]).data_ptr(), float(loss["world"]), float(loss["sparse_w"])):
+            raise ValueError("hashnerf_amd.render_bwd: prepass_done, but the loss (target, world, sparse_w) "
+                             "is not the one the forward took")
     if getattr(st, "skip_dead", False):
         # only the binned dense_bwd = 0 backward runs lists of the tiles that were stored
         if st.cfg.dense_bwd:
@@ -405,6 +455,9 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
         la.out = loss["out"].data_ptr()
         a.loss = C.pointer(la)
         keep += ts + [ltv, la]
+    if prepass_done:
+        a.prepass_done = 1
+        st.prepass_done = None   # the backward clears the forward's stamp
     t0 = TIMER.begin("render_bwd")
     L.check(L.lib().hn_render_bwd(st.cfg, a, L.ptr(st.wsb), st.nbytes, L.stream(dev)), "render_bwd")
     TIMER.end("render_bwd", t0)

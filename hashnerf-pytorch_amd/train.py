@@ -610,6 +610,10 @@ class Trainer:
         # backward's composite pre-pass (ABI 13) instead of an hn_loss_fwd_bwd
         # launch
         self.fuse_loss = True
+        # ... and, one GPU with the binned backward, that composite backward run by
+        # the forward's own waves on the raw / z they still hold (no pre-pass
+        # launch; False keeps the pre-pass, for the A/B: bitwise the same step)
+        self.fuse_prepass = True
         self._side = None
         # the backward skips the samples whose d raw is exactly zero (relu(sigma)
         # = 0: no gradient at all; hn_render_cfg.dense_bwd, ABI 14): True
@@ -853,9 +857,16 @@ class Trainer:
         # the colour net of tiles without any density is skipped (the trainer never
         # returns raw rgb; with dense_bwd everything is computed, for the A/B) --
         # where the binned backward follows: the float-atomic one loads every tile
+        # one GPU, binned backward, loss formed in the backward: the targets are
+        # known before the forward, so each ray's forward wave runs the loss's
+        # composite backward itself (d raw and the marks left in the workspace)
+        # and the backward launches no pre-pass
+        fold = self.fuse_prepass and self.fuse_loss and self._binned and self.world == 1
         out, st = HF.render_fwd(self._cfg, rays, self._t_vals, t_rand, u, None, None, table, self._ws, True,
                                 wsb=self._rws, weights_packed=self._pk is not None and self._pk == self._pack_key(),
-                                skip_dead_color=(not self._cfg.dense_bwd) and self._binned)
+                                skip_dead_color=(not self._cfg.dense_bwd) and self._binned,
+                                loss=dict(target=target, world=self.world, sparse_w=a.sparse_loss_weight)
+                                if fold else None)
         self._pk = None
         if pf:
             self._prefetch(i + 1)
@@ -896,7 +907,7 @@ class Trainer:
             mstep = [self.optimizer.take_step(p) for p in self._ws] if self.fuse_mlp_step else None
             HF.render_bwd(st, grads, None, self._gws, table_step=self.optimizer.take_step(table),
                           overwrite_mlp=True, tv=tvb, table_live=self._live_mask(), loss=loss, mlp_step=mstep,
-                          repack=mstep is not None)
+                          repack=mstep is not None, prepass_done=fold)
             if mstep is not None:
                 self._pk = self._pack_key()   # the workspace holds the stepped weights' copies
             table.grad = None
@@ -906,7 +917,7 @@ class Trainer:
             # DP exchange its owner pass runs per segment inside the exchange
             defer = self._xchg is not None and self._xchg.seg_bins is not None
             HF.render_bwd(st, grads, self._gtable, self._gws, overwrite=True, overwrite_mlp=True, tv=tvb,
-                          owner_defer=defer, loss=loss)
+                          owner_defer=defer, loss=loss, prepass_done=fold)
             self._owner_st = st if defer else None
             table.grad = self._gtable
         for p, g in zip(self._ws, self._gws):

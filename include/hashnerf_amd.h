@@ -24,6 +24,10 @@
 extern "C" {
 #endif
 
+/* 14 also covers two additive fields appended at the end of their structs,
+ * where zero / NULL keeps the earlier behaviour: hn_render_fwd_args.loss and
+ * hn_render_bwd_args.prepass_done (a caller built against the shorter structs
+ * must zero-fill the args, as every caller of this ABI does). */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
 
@@ -218,6 +222,14 @@ typedef struct hn_render_fwd_args {
                                float-atomic schedule and a dense_bwd = 1 backward load every tile,
                                so either one of this state is invalid.  0 = every sample's raw
                                rgb computed (the reference's `raw` output), every tile stored */
+  const hn_render_loss* loss;   /* additive under ABI 14 (NULL = the forward as before): the training loss
+                               whose gradient the following hn_render_bwd takes (of this struct only target,
+                               world and sparse_w are read here).  Each ray's forward wave then also runs
+                               the composite backward of its two passes and leaves d raw and the work
+                               marks in `workspace`, with a stamp for n_rays; the one hn_render_bwd that
+                               follows on this workspace sets prepass_done and launches no pre-pass --
+                               bitwise the same gradients.  Binned scatter only (hn_render_scatter_mode
+                               == 2, else HN_E_SHAPE).  Every output of the forward is unchanged */
 } hn_render_fwd_args;
 
 typedef struct hn_render_bwd_args {
@@ -289,6 +301,14 @@ typedef struct hn_render_bwd_args {
   int32_t repack;           /* ABI 13, with mlp_step: then write the stepped weights' packed MFMA copies
                                into `workspace` (in the overflow-placement launch), so the next
                                hn_render_fwd on this workspace may set weights_packed */
+  int32_t prepass_done;     /* additive under ABI 14 (0 = as before): the hn_render_fwd of these rays on this
+                               workspace ran with the same `loss` (target, world, sparse_w), so d raw and
+                               the marks are in the workspace and the composite pre-pass is not launched.
+                               Needs the binned scatter, `loss` (its value is still reduced here) and no
+                               g_rgb / g_rgb0 / g_raw_f (else HN_E_SHAPE).  The first kernel checks the
+                               forward's stamp on the device: absent, for another n_rays, or already used
+                               by a backward, it sets fault bit 128 (hn_device_faults) and the launch
+                               computes no ray's gradient */
 } hn_render_bwd_args;
 
 /* The binned scatter's bins for this cfg and batch: returns their number (0:
