@@ -72,27 +72,6 @@ class HnRadamTensor(C.Structure):
                 ("reserved", C.c_int32)]
 
 
-class HnRenderBwdArgs(C.Structure):
-    _fields_ = [("n_rays", C.c_int64), ("rays", _P), ("noise_c", _P), ("noise_f", _P), ("table", _P),
-                ("coarse", HnMlp), ("fine", HnMlp), ("z_coarse", _P), ("z_fine", _P), ("raw_c", _P),
-                ("raw_f", _P), ("fine_src", _P), ("feat", _P), ("weights_packed", C.c_int32),
-                ("d_table_mode", C.c_int32), ("g_rgb", _P), ("g_depth", _P), ("g_acc", _P), ("g_sparsity", _P),
-                ("g_rgb0", _P), ("g_depth0", _P), ("g_acc0", _P), ("g_sparsity0", _P),
-                ("g_raw_f", _P), ("d_table", _P), ("d_coarse", HnMlpGrad), ("d_fine", HnMlpGrad),
-                ("table_step", C.POINTER(HnRadamTensor)), ("tv", C.c_void_p), ("g_tv", _P),
-                ("table_live", _P), ("table_live_levels", C.c_int32), ("owner_defer", C.c_int32),
-                ("loss", C.POINTER(HnRenderLoss)), ("mlp_step", C.POINTER(HnRadamTensor)),
-                ("repack", C.c_int32), ("prepass_done", C.c_int32)]
-
-
-class HnTvArgs(C.Structure):
-    _fields_ = [("n_levels", C.c_int32), ("log2_hashmap_size", C.c_int32),
-                ("cube", C.c_int32 * MAX_LEVELS), ("min_vertex", _P), ("table", _P)]
-
-
-RADAM_MAX_TENSORS = 16
-
-
 class HnRaySampler(C.Structure):
     _fields_ = [("H", C.c_int32), ("W", C.c_int32), ("crop_y0", C.c_int32), ("crop_x0", C.c_int32),
                 ("crop_h", C.c_int32), ("crop_w", C.c_int32), ("fx", C.c_float), ("fy", C.c_float),
@@ -105,6 +84,34 @@ class HnUniformDraw(C.Structure):
 
 
 UNIFORM_MAX_DRAWS = 4
+
+
+class HnNextBatch(C.Structure):
+    """hn_next_batch: hn_sample_batch_morton's arguments, as a job of hn_render_bwd."""
+    _fields_ = [("sampler", C.POINTER(HnRaySampler)), ("image", _P), ("c2w", _P), ("n_rays", C.c_int64),
+                ("rays", _P), ("target", _P), ("workspace", _P), ("ws_bytes", C.c_size_t), ("seed", C.c_uint64),
+                ("draws", C.POINTER(HnUniformDraw)), ("n_draws", C.c_int32)]
+
+
+class HnRenderBwdArgs(C.Structure):
+    _fields_ = [("n_rays", C.c_int64), ("rays", _P), ("noise_c", _P), ("noise_f", _P), ("table", _P),
+                ("coarse", HnMlp), ("fine", HnMlp), ("z_coarse", _P), ("z_fine", _P), ("raw_c", _P),
+                ("raw_f", _P), ("fine_src", _P), ("feat", _P), ("weights_packed", C.c_int32),
+                ("d_table_mode", C.c_int32), ("g_rgb", _P), ("g_depth", _P), ("g_acc", _P), ("g_sparsity", _P),
+                ("g_rgb0", _P), ("g_depth0", _P), ("g_acc0", _P), ("g_sparsity0", _P),
+                ("g_raw_f", _P), ("d_table", _P), ("d_coarse", HnMlpGrad), ("d_fine", HnMlpGrad),
+                ("table_step", C.POINTER(HnRadamTensor)), ("tv", C.c_void_p), ("g_tv", _P),
+                ("table_live", _P), ("table_live_levels", C.c_int32), ("owner_defer", C.c_int32),
+                ("loss", C.POINTER(HnRenderLoss)), ("mlp_step", C.POINTER(HnRadamTensor)),
+                ("repack", C.c_int32), ("prepass_done", C.c_int32), ("next_batch", C.POINTER(HnNextBatch))]
+
+
+class HnTvArgs(C.Structure):
+    _fields_ = [("n_levels", C.c_int32), ("log2_hashmap_size", C.c_int32),
+                ("cube", C.c_int32 * MAX_LEVELS), ("min_vertex", _P), ("table", _P)]
+
+
+RADAM_MAX_TENSORS = 16
 
 
 class HnRayPool(C.Structure):

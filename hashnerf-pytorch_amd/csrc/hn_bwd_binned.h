@@ -2,6 +2,7 @@
 // benchmark line and nearly every test runs it.  Its kernels, in launch
 // order after render_comp_bwd_kernel's pre-pass:
 //   render_lists_kernel   lists of the 16-sample groups with a nonzero d raw
+//                         (+ the next batch's tile counts and uniform draws)
 //   render_bwd_kernel     <kSwVmcnt, kModeSplit>: 1,024 waves on equal slices
 //                         of the coarse and fine lists (b1_groups), feature
 //                         grads stored per point, one dW slab per run of waves
@@ -9,15 +10,30 @@
 //                         x-pairs, staged through LDS), the TV term's
 //                         records, then the dW slabs' reduction with the
 //                         NeRFSmall RAdam steps
-//   ovf_place_kernel      spilled records bucketed by bin (+ the repack)
+//   ovf_place_kernel      spilled records bucketed by bin (+ the repack,
+//                         + the next batch's rays)
 //   bin_reduce_kernel     the owner pass: exact fixed-point sums per bin, the
 //                         table gradient written once, or the fused table step
 // No float atomic reaches memory and every sum has a fixed order, so the
 // gradients are bitwise reproducible.
 #pragma once
 #include "hn_mlp_bwd.h"
+#include "hn_sampler.h"
 
 namespace hn {
+
+// hn_render_bwd_args.next_batch: the next step's Morton draw and uniform
+// draws (hn_sampler.h), run by workgroups appended to the two small launches
+// of this schedule -- pass 1 and the uniforms behind the lists kernel's own
+// workgroups, pass 2 behind the placement kernel's, the scatter and MLP
+// kernels between them being the boundary the passes need.  `first` = the
+// launch's own workgroups (its workgroups from `first` on belong to the job;
+// without a job there are none).
+struct NextK {
+  MortonK m;
+  UniK u;
+  unsigned first;
+};
 
 // ---- binned table-gradient scatter ------------------------------------------
 // The memory-side float-atomic rate (~20 G requests/s, one per 64-B segment
@@ -820,12 +836,20 @@ HN_DEV int list_block_sum(int v, int* sh) {
 // raises kFaultPrepass, leaves the lists alone and reports them empty.  The
 // workgroup whose add came last clears the stamp: one backward per training
 // forward.
-__global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k, unsigned long long* stamp) {
+__global__ __launch_bounds__(kListThreads) void render_lists_kernel(B1K k, unsigned long long* stamp, NextK nk) {
   static_assert(kListThreads == 256, "list_block_scan: 4 waves");
+  if (blockIdx.x >= nk.first) {   // the next batch: dispatched behind the lists' own workgroups
+    const unsigned j = blockIdx.x - nk.first;
+    if (j < nk.m.blocks)
+      morton_count_block<kListThreads>(nk.m, j);
+    else
+      uniform_block<kListThreads>(nk.u, j - nk.m.blocks);
+    return;
+  }
   __shared__ int sh[3][4];
   __shared__ int stamp_ok;
   const int t = threadIdx.x;
-  int bx = (int)blockIdx.x, nbx = (int)gridDim.x;
+  int bx = (int)blockIdx.x, nbx = (int)nk.first;
   unsigned long long seen = 0ull;
   if (stamp) {
     if (t == 0) seen = __hip_atomic_fetch_add(stamp, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -1033,7 +1057,14 @@ struct PackK {
   hn_mlp c, f;
   float* P;   // [2][G_END]: the workspace's packed copies (hn_render_fwd's Pc, Pf)
 };
-__global__ __launch_bounds__(kPlaceThreads) void ovf_place_kernel(BinR k, PackK pk) {
+static_assert(kPlaceThreads == kMortonThreads, "morton_emit_block: one thread per Morton index of a tile");
+// next / first: the next batch's pass 2 in the workgroups from `first` on
+// (NextK; first = the placement and repack workgroups)
+__global__ __launch_bounds__(kPlaceThreads) void ovf_place_kernel(BinR k, PackK pk, MortonK next, unsigned first) {
+  if (blockIdx.x >= first) {
+    morton_emit_block(next, blockIdx.x - first);
+    return;
+  }
   if (blockIdx.x >= kBwdBlocks) {
     const int idx = (int)(blockIdx.x - kBwdBlocks) * kPlaceThreads + (int)threadIdx.x;
     if (idx < 2 * G_END) pk.P[idx] = idx < G_END ? pack_value(pk.c, idx) : pack_value(pk.f, idx - G_END);

@@ -457,7 +457,8 @@ static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a
   hn_render_bwd_args b = *a;
   b.n_rays = 0;
   const BinR r = owner_args(cfg, &b, bins, bg, 0);
-  hipLaunchKernelGGL(ovf_place_kernel, dim3(kBwdBlocks), dim3(kPlaceThreads), 0, s, r, PackK{});
+  hipLaunchKernelGGL(ovf_place_kernel, dim3(kBwdBlocks), dim3(kPlaceThreads), 0, s, r, PackK{}, MortonK{},
+                     (unsigned)kBwdBlocks);
   if ((st = hip_status(hipGetLastError()))) return st;
   launch_owner(r, bg, bg.nbins, s);
   return hip_status(hipGetLastError());
@@ -466,9 +467,10 @@ static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a
 // The binned schedule (hn_bwd_binned.h): pre-pass, lists, MLP backward,
 // scatter into records (+ the TV term's, tv != NULL; + the dW slabs'
 // reduction and the MLP steps), overflow placement (+ the repack), owner pass
-// unless deferred to hn_render_bwd_owner.
+// unless deferred to hn_render_bwd_owner.  nk: the next batch's job (NextK;
+// validated, no workgroups without one) in the lists and placement launches.
 static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a, const BwdPlan& plan, const B1K& k,
-                          const hn_tv_args* tv, const TvK& tvk, void* workspace, hipStream_t s) {
+                          const hn_tv_args* tv, const TvK& tvk, NextK& nk, void* workspace, hipStream_t s) {
   int32_t st;
   // prepass_done: the training forward left d raw and the marks; the lists
   // kernel checks its stamp and takes the pre-pass's side jobs in one extra
@@ -480,8 +482,10 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                        dim3(64 * kFwdWaves), 0, s, k);
   // the backward's work lists (from the marks)
   const int64_t nlb = (a->n_rays + kListThreads - 1) / kListThreads;
-  hipLaunchKernelGGL(render_lists_kernel, dim3((unsigned)(nlb < kListMaxBlocks ? nlb : kListMaxBlocks) + prepass),
-                     dim3(kListThreads), 0, s, k, prepass ? ws_stamp(k.lmeta) : nullptr);
+  // (+ the next batch's tile counts and uniform draws, dispatched behind them)
+  nk.first = (unsigned)(nlb < kListMaxBlocks ? nlb : kListMaxBlocks) + prepass;
+  hipLaunchKernelGGL(render_lists_kernel, dim3(nk.first + (nk.m.n ? nk.m.blocks + uni_blocks(nk.u) : 0u)),
+                     dim3(kListThreads), 0, s, k, prepass ? ws_stamp(k.lmeta) : nullptr, nk);
   if ((st = hip_status(hipGetLastError()))) return st;
   hipLaunchKernelGGL((render_bwd_kernel<kSwVmcnt, kModeSplit>), dim3(kBwdBlocks), dim3(64 * kB1Waves),
                      (size_t)kB1LdsF * sizeof(float), s, k);
@@ -519,7 +523,10 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
     pk.P = (float*)workspace;
     pblocks = (unsigned)((2 * G_END + kPlaceThreads - 1) / kPlaceThreads);
   }
-  hipLaunchKernelGGL(ovf_place_kernel, dim3(kBwdBlocks + pblocks), dim3(kPlaceThreads), 0, s, r, pk);
+  // (+ the next batch's rays: every tile's count is in place since the lists launch)
+  const unsigned own = (unsigned)kBwdBlocks + pblocks;
+  hipLaunchKernelGGL(ovf_place_kernel, dim3(own + (nk.m.n ? nk.m.blocks : 0u)), dim3(kPlaceThreads), 0, s, r, pk,
+                     nk.m, own);
   if ((st = hip_status(hipGetLastError()))) return st;
   if (!a->owner_defer) {
     launch_owner(r, plan.bg, plan.bg.nbins, s);
@@ -562,6 +569,8 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   if (st) return st;
   if (!a) return HN_E_NULL;
   if (a->n_rays < 0) return HN_E_SHAPE;
+  // the next batch rides the lists and placement launches of a backward that runs both
+  if (a->next_batch && (a->n_rays == 0 || a->owner_defer)) return HN_E_SHAPE;
   if (a->n_rays == 0) return a->tv ? tv_only_bwd(cfg, a, workspace, ws_bytes, (hipStream_t)stream) : HN_OK;
   if (!a->rays || !a->table || !mlp_ok(a->coarse) || !mlp_ok(a->fine)) return HN_E_NULL;
   if (!a->z_coarse || !a->z_fine || !a->raw_c || !a->raw_f || !a->fine_src || !a->feat)
@@ -572,6 +581,16 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   const BwdPlan plan = bwd_plan(cfg, a->n_rays);
   const bool binned = plan.mode == kModeSplit;
   if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
+  // the next batch's job: hn_sample_batch_morton's checks and codes, before anything is queued
+  NextK nk{};
+  if (a->next_batch) {
+    if (!binned) return HN_E_SHAPE;
+    const hn_next_batch& nb = *a->next_batch;
+    if ((st = make_uni(nb.seed, nb.draws, nb.n_draws, nk.u))) return st;
+    if ((st = make_morton(nb.sampler, nb.image, nb.c2w, nb.n_rays, nb.rays, nb.target, nb.workspace, nb.ws_bytes,
+                          nk.m)))
+      return st;
+  }
   // the weights' packed copies: the one launch ahead of the remaining checks
   // (its status, where it fails, decides before theirs)
   hipStream_t s = (hipStream_t)stream;
@@ -672,7 +691,8 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
 
   // ---- one schedule; then, under either, a TV term that is not in the
   // records: hn_tv_bwd's atomics into d_table ----
-  if ((st = binned ? bwd_binned(cfg, a, plan, k, tv_rec, tvk, workspace, s) : bwd_atomic(cfg, a, k, s))) return st;
+  if ((st = binned ? bwd_binned(cfg, a, plan, k, tv_rec, tvk, nk, workspace, s) : bwd_atomic(cfg, a, k, s)))
+    return st;
   if (tv_atomic) return hn_tv_bwd(tv_atomic, a->g_tv, a->d_table, stream);
   return HN_OK;
 }

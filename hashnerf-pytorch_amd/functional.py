@@ -316,7 +316,7 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
 
 def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = False, table_step=None,
                overwrite_mlp: bool = False, tv=None, table_live=None, owner_defer: bool = False, loss=None,
-               mlp_step=None, repack: bool = False, prepass_done: bool = False):
+               mlp_step=None, repack: bool = False, prepass_done: bool = False, next_batch=None):
     """hn_render_bwd: accumulates (+=) d loss / d table into d_table (or
     writes it, overwrite=True: d_table need not be zeroed) and the ten
     NeRFSmall weight gradients into dws (coarse 5, fine 5, +=; written with
@@ -351,7 +351,12 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     launched.  Refused here when st's forward did not (or another such
     forward has used the workspace since, or a backward has consumed it);
     the library checks the forward's stamp on the device as well (fault
-    bit 128)."""
+    bit 128).
+    next_batch = a NextBatch (functional.next_batch; binned scatter, no
+    owner_defer): the next step's rays, targets and uniform draws are made by
+    extra workgroups of this backward's lists and placement launches instead
+    of the sampler's own two launches -- bitwise sample_rays' values, in
+    next_batch.out once this call's launches have run."""
     B = st.rays.shape[0]
     dev = st.rays.device
     if prepass_done:
@@ -455,6 +460,9 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
         la.out = loss["out"].data_ptr()
         a.loss = C.pointer(la)
         keep += ts + [ltv, la]
+    if next_batch is not None:
+        a.next_batch = C.pointer(next_batch.job)
+        keep.append(next_batch)
     if prepass_done:
         a.prepass_done = 1
         st.prepass_done = None   # the backward clears the forward's stamp
@@ -578,6 +586,56 @@ def torch_uniform(shapes, dev):
     return outs
 
 
+def _ray_sampler(image, c2w, K, near, far, crop, seed):
+    """hn_ray_sampler of one image and window, and the contiguous image and
+    [3, 4] pose it is used with."""
+    L.require_device(image, c2w)
+    image, c2w = image.contiguous(), c2w[:3, :4].contiguous()
+    s = L.HnRaySampler()
+    s.H, s.W = image.shape[0], image.shape[1]
+    s.crop_y0, s.crop_x0, s.crop_h, s.crop_w = (int(v) for v in crop)
+    s.fx, s.fy, s.cx, s.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+    s.near, s.far = float(near), float(far)
+    s.seed = int(seed) & ((1 << 64) - 1)
+    return s, image, c2w
+
+
+class NextBatch:
+    """sample_rays(order=1, uniforms=...) as a job of render_bwd
+    (hn_render_bwd_args.next_batch): ``job`` the hn_next_batch, ``out`` =
+    (rays, target, *uniform tensors) that the backward's launches fill."""
+    __slots__ = ("job", "out", "keep")
+
+
+def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None):
+    """The host half of sample_rays(image, ..., order=1, uniforms=uniforms):
+    the sampler's arguments, the output tensors and the default generator's
+    philox offsets (advanced as the torch.rand calls would), without the
+    launches.  render_bwd(next_batch=...) of the binned schedule runs the
+    device half inside its own two small launches, bitwise the values
+    sample_rays would return."""
+    s, image, c2w = _ray_sampler(image, c2w, K, near, far, crop, seed)
+    dev = image.device
+    nb = L.lib().hn_sample_rays_morton_workspace_bytes(s)
+    if nb == 0:
+        raise ValueError(f"next_batch: window {s.crop_h}x{s.crop_w} too large")
+    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
+    target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+    ws = _sampler_ws(dev, nb)
+    useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
+    j = L.HnNextBatch()
+    j.sampler = C.pointer(s)
+    j.image, j.c2w, j.n_rays = image.data_ptr(), c2w.data_ptr(), n_rays
+    j.rays, j.target = rays.data_ptr(), target.data_ptr()
+    j.workspace, j.ws_bytes = ws.data_ptr(), nb
+    j.seed, j.n_draws = useed, len(outs)
+    if arr is not None:
+        j.draws = arr
+    b = NextBatch()
+    b.job, b.out, b.keep = j, (rays, target, *outs), (s, image, c2w, ws, arr)
+    return b
+
+
 def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=None):
     """N_rand distinct pixels of one image (device, no replacement) -> the
     [n, 11] ray batch render() builds and the [n, 3] target colours.
@@ -590,15 +648,7 @@ def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=
     order.  Both are deterministic for a given seed.  uniforms: shapes of
     torch.rand draws to make as well (torch_uniform; with order=1 in the
     sampler's first launch), returned after rays and target."""
-    L.require_device(image, c2w)
-    image, c2w = image.contiguous(), c2w[:3, :4].contiguous()
-    H, W = image.shape[0], image.shape[1]
-    s = L.HnRaySampler()
-    s.H, s.W = H, W
-    s.crop_y0, s.crop_x0, s.crop_h, s.crop_w = (int(v) for v in crop)
-    s.fx, s.fy, s.cx, s.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-    s.near, s.far = float(near), float(far)
-    s.seed = int(seed) & ((1 << 64) - 1)
+    s, image, c2w = _ray_sampler(image, c2w, K, near, far, crop, seed)
     dev = image.device
     rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
     target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)

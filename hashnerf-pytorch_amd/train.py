@@ -19,6 +19,7 @@ from __future__ import annotations
 
 import math
 import types
+import warnings
 from typing import Optional
 
 import numpy as np
@@ -597,6 +598,22 @@ class Trainer:
         # cross-stream waits cost more than the launches they move), so off
         # unless asked for (bench.py --prefetch).
         self.prefetch = False
+        # self-driving loops again, without a second stream: the next step's
+        # batch is drawn inside this step's render backward, whose two small
+        # launches (work lists, overflow placement) leave nearly every CU
+        # idle and take the sampler's two passes as extra workgroups
+        # (hn_render_bwd_args.next_batch) -- no sampler launch ahead of the
+        # next forward.  In effect only where _fuses_next_batch() holds (one
+        # GPU, binned schedule with the fused table step, the per-image Morton
+        # sampler, prefetch off: the two cannot both draw the next batch, and
+        # prefetch, the one asked for, wins) and only in a step() called
+        # without an index or a batch.  Step i then draws batch i + 1 in
+        # draw_batch's order (image, philox offsets, TV cubes) before its
+        # backward, and draw_batch(i + 1) hands that batch out -- to the next
+        # step() or to a caller -- so every trajectory is bitwise the same.
+        self.fuse_next_batch = True
+        self._nb = None          # (step, batch) drawn by the previous step's backward
+        self._binned = False     # (set by _fused_setup)
         # one GPU, fused table step: the MLP tensors' RAdam steps run in the
         # backward's slab reduction too (no hn_radam_step launch)
         self.fuse_mlp_step = True
@@ -785,6 +802,18 @@ class Trainer:
         Returns a dict rays [B, 11], target [B, 3], t_rand, u, tv (or None)."""
         a, d, kw = self.args, self.data, self.kw_train
         i = self.global_step + 1 if i is None else i
+        if self._nb is not None:
+            # the batch the previous step's backward drew (fuse_next_batch)
+            (j, batch), self._nb = self._nb, None
+            if j == i:
+                return batch
+            if self._fuses_next_batch():
+                self._nb = (j, batch)
+                raise RuntimeError(f"Trainer.draw_batch({i}): the last step() drew the batch of step {j} ahead "
+                                   "(Trainer.fuse_next_batch) and its random numbers are taken; draw that "
+                                   "step's batch first, or turn fuse_next_batch off before the loop")
+            warnings.warn(f"Trainer.draw_batch({i}): dropping the batch of step {j}, drawn ahead before the "
+                          "trainer's settings left fuse_next_batch's mode (its random numbers stay consumed)")
         perturb = kw.get("perturb", 0.) > 0.
         # two draws in render_rays' order (run_nerf_helpers.py:528, then :276 via :548): the
         # autograd and reference-path modes draw them the same way, so all
@@ -799,11 +828,39 @@ class Trainer:
             t_rand = torch.rand((B, kw["N_samples"]), device=self.device) if perturb else None
             u = (torch.rand((B, kw["N_importance"]), device=self.device) if perturb else
                  torch.linspace(0., 1., kw["N_importance"], device=self.device).expand(B, kw["N_importance"]))
-        tv = None
+        return dict(rays=rays, target=target, t_rand=t_rand, u=u, tv=self._draw_tv(i))
+
+    def _draw_tv(self, i: int):
+        """Step i's TV cubes + min vertices (rank 0, i <= tv_until), or None."""
+        a = self.args
         if a.tv_loss_weight > 0 and self.rank == 0 and i <= a.tv_until:
-            tv = draw_tv_cubes(self.embed_fn.n_levels, self.embed_fn.base_resolution,
-                               self.embed_fn.finest_resolution, self.cpu_gen)
-        return dict(rays=rays, target=target, t_rand=t_rand, u=u, tv=tv)
+            return draw_tv_cubes(self.embed_fn.n_levels, self.embed_fn.base_resolution,
+                                 self.embed_fn.finest_resolution, self.cpu_gen)
+        return None
+
+    def _fuses_next_batch(self):
+        """Whether a self-driven step draws the next batch inside its render
+        backward (fuse_next_batch): the backward must run the lists and
+        placement launches and the owner pass itself (one GPU, binned
+        schedule, fused table step), and the batch must be the per-image
+        Morton sampler's with its uniform draws."""
+        return bool(self.fuse_next_batch and not self.prefetch and self.mode == "explicit" and self.world == 1
+                    and self.device.type == "cuda" and not self.use_batching and self.ray_order == 1
+                    and self._binned and self.fuse_table_step and self.kw_train.get("perturb", 0.) > 0.)
+
+    def _draw_next(self, i: int):
+        """draw_batch(i) with the device half left to a render backward: the
+        host half in draw_batch's order (image, step seed, the default
+        generator's philox offsets, TV cubes).  Returns the batch, whose
+        tensors that backward fills, and the job for render_bwd."""
+        a, d, kw = self.args, self.data, self.kw_train
+        img_i = self._train_image()
+        crop = self.crop if i < a.precrop_iters else (0, 0, d.H, d.W)
+        nb = HF.next_batch(d.images[img_i], d.poses[img_i], a.N_rand, d.K, 2., 6., crop,
+                           _step_seed(self.seed, self.rank, i),
+                           uniforms=[(a.N_rand, kw["N_samples"]), (a.N_rand, kw["N_importance"])])
+        rays, target, t_rand, u = nb.out
+        return dict(rays=rays, target=target, t_rand=t_rand, u=u, tv=self._draw_tv(i)), nb
 
     def _prefetch(self, i: int):
         """draw_batch(i) on the side stream, after the work enqueued so far on
@@ -833,7 +890,7 @@ class Trainer:
                 pf[1][k].record_stream(cur)
         return pf[1]
 
-    def _fused_forward_backward(self, i: int, batch=None):
+    def _fused_forward_backward(self, i: int, batch=None, self_driven=False):
         a = self.args
         if self._grads is None:
             self._fused_setup()
@@ -905,9 +962,17 @@ class Trainer:
             # the MLP groups' steps likewise, where the slab reduction forms
             # their gradients (optimizer.step() then has nothing left)
             mstep = [self.optimizer.take_step(p) for p in self._ws] if self.fuse_mlp_step else None
+            # a self-driven loop: batch i + 1 drawn by this backward's lists and
+            # placement launches (fuse_next_batch), into tensors of its own --
+            # this backward still reads step i's target and rays
+            nxt = job = None
+            if self_driven and self._fuses_next_batch():
+                nxt, job = self._draw_next(i + 1)
             HF.render_bwd(st, grads, None, self._gws, table_step=self.optimizer.take_step(table),
                           overwrite_mlp=True, tv=tvb, table_live=self._live_mask(), loss=loss, mlp_step=mstep,
-                          repack=mstep is not None, prepass_done=fold)
+                          repack=mstep is not None, prepass_done=fold, next_batch=job)
+            if nxt is not None:
+                self._nb = (i + 1, nxt)
             if mstep is not None:
                 self._pk = self._pack_key()   # the workspace holds the stepped weights' copies
             table.grad = None
@@ -980,11 +1045,12 @@ class Trainer:
         i > 1000 is formed, run_nerf.py:636-638), and the lr set after the
         step from the pre-increment global_step (:647-651)."""
         a = self.args
+        self_driven = i is None and batch is None   # the loop is the trainer's own: fuse_next_batch may draw ahead
         i = self.global_step + 1 if i is None else i
         if batch is not None and self.mode != "explicit":
             raise ValueError("Trainer.step(batch=...) needs mode='explicit'")
         if self.mode == "explicit":
-            loss, mse = self._fused_forward_backward(i, batch)
+            loss, mse = self._fused_forward_backward(i, batch, self_driven)
         else:
             self.optimizer.zero_grad(set_to_none=True)
             if self.mode == "autograd":

@@ -24,9 +24,9 @@
 extern "C" {
 #endif
 
-/* 14 also covers two additive fields appended at the end of their structs,
- * where zero / NULL keeps the earlier behaviour: hn_render_fwd_args.loss and
- * hn_render_bwd_args.prepass_done (a caller built against the shorter structs
+/* 14 also covers three additive fields appended at the end of their structs,
+ * where zero / NULL keeps the earlier behaviour: hn_render_fwd_args.loss,
+ * hn_render_bwd_args.prepass_done and .next_batch (a caller built against the shorter structs
  * must zero-fill the args, as every caller of this ABI does). */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
@@ -309,6 +309,12 @@ typedef struct hn_render_bwd_args {
                                forward's stamp on the device: absent, for another n_rays, or already used
                                by a backward, it sets fault bit 128 (hn_device_faults) and the launch
                                computes no ray's gradient */
+  const struct hn_next_batch* next_batch;   /* additive under ABI 14 (NULL = as before): the next step's batch
+                               (hn_next_batch below: hn_sample_batch_morton's arguments) drawn inside this
+                               backward's two small launches.  Binned scatter with its owner pass here only:
+                               HN_E_SHAPE with the float-atomic schedule, with n_rays == 0 and with owner_defer.
+                               Checked as hn_sample_batch_morton checks it, with its return codes, before
+                               anything is queued */
 } hn_render_bwd_args;
 
 /* The binned scatter's bins for this cfg and batch: returns their number (0:
@@ -404,6 +410,29 @@ int32_t hn_uniform_philox(uint64_t seed, const hn_uniform_draw* draws, int32_t n
 int32_t hn_sample_batch_morton(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
                                float* rays, float* target, void* workspace, size_t ws_bytes, uint64_t seed,
                                const hn_uniform_draw* draws, int32_t n_draws, void* stream);
+/* The same call as a job of hn_render_bwd (hn_render_bwd_args.next_batch): a
+ * training loop's next batch depends on nothing its current step computes, so
+ * the binned backward runs the sampler's two passes as extra workgroups of its
+ * own two small launches, which a kernel boundary separates as the passes
+ * need -- the tile counts and the uniform draws behind the work lists'
+ * workgroups, the emit behind the overflow placement's -- instead of two
+ * launches ahead of the next forward.  The fields are hn_sample_batch_morton's
+ * arguments (sampler and draws: host pointers read at call time); every
+ * output is bitwise that call's.  rays / target / the draws' outputs /
+ * workspace must not be buffers the backward itself reads or writes. */
+typedef struct hn_next_batch {
+  const hn_ray_sampler* sampler;
+  const float* image;
+  const float* c2w;
+  int64_t n_rays;
+  float* rays;
+  float* target;
+  void* workspace;
+  size_t ws_bytes;
+  uint64_t seed;
+  const hn_uniform_draw* draws;
+  int32_t n_draws;
+} hn_next_batch;
 
 /* use_batching ray pool (run_nerf.py:505-521 builds rays_rgb from every training
  * pixel and shuffles it; :544-555 takes consecutive N_rand slices and reshuffles
