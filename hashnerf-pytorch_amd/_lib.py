@@ -120,6 +120,8 @@ class HnRayPool(C.Structure):
                 ("near", C.c_float), ("far", C.c_float), ("seed", C.c_uint64)]
 
 
+POOL_ORDER_MAX = 8192           # HN_POOL_ORDER_MAX
+
 # name -> (restype, argtypes); must match include/hashnerf_amd.h exactly.
 SIGNATURES = {
     "hn_abi_version": (C.c_int32, []),
@@ -148,6 +150,9 @@ SIGNATURES = {
     "hn_sample_rays_morton": (C.c_int32, [C.POINTER(HnRaySampler), _P, _P, C.c_int64, _P, _P, _P, C.c_size_t,
                                           _P]),
     "hn_sample_pool": (C.c_int32, [C.POINTER(HnRayPool), _P, _P, _P, C.c_int64, C.c_int64, _P, _P, _P]),
+    "hn_sample_pool_ordered": (C.c_int32, [C.POINTER(HnRayPool), _P, _P, _P, C.c_int64, C.c_int64,
+                                           C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, C.c_uint64,
+                                           C.POINTER(HnUniformDraw), C.c_int32, _P]),
     "hn_blender_images": (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "hn_loss_fwd": (C.c_int32, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                                 C.c_float, _P, _P]),

@@ -169,6 +169,132 @@ HN_DEV void morton_emit_block(const MortonK& k, unsigned b) {
 }
 
 // ---------------------------------------------------------------------------
+// use_batching ray pool: position q of the epoch's shuffle -> its ray (11
+// floats at `out`) and target colour (3 at `tgt`).  hn_sample_pool writes the
+// positions in order, hn_sample_pool_ordered in Morton order of their keys --
+// the same function, so the same 14 floats.
+// ---------------------------------------------------------------------------
+HN_DEV void pool_ray(const hn_ray_pool& p, const float* __restrict__ images, const float* __restrict__ poses,
+                     const int32_t* __restrict__ ids, int half, uint32_t q, float* __restrict__ out,
+                     float* __restrict__ tgt) {
+  const uint32_t hw = (uint32_t)p.H * (uint32_t)p.W;
+  const uint32_t N = (uint32_t)p.n_images * hw;
+  uint32_t x = q;
+  do {
+    x = feistel(x, half, p.seed);
+  } while (x >= N);
+  const int img = ids[x / hw];
+  const uint32_t pix = x % hw;
+  const int py = (int)(pix / (uint32_t)p.W), px = (int)(pix % (uint32_t)p.W);
+  const float* c = poses + (size_t)img * p.pose_stride;
+  // dirs = [(i - K[0][2]) / K[0][0], -(j - K[1][2]) / K[1][1], -1] (float64: K is)
+  const double d0 = ((double)px - p.cx) / p.fx;
+  const double d1 = -((double)py - p.cy) / p.fy;
+  const double d2 = -1.0;
+  float d[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {   // np.sum(dirs[..., None, :] * c2w[:3, :3], -1): ((p0 + p1) + p2)
+    d[a] = (float)((d0 * (double)c[4 * a] + d1 * (double)c[4 * a + 1]) + d2 * (double)c[4 * a + 2]);
+    out[a] = c[4 * a + 3];
+    out[3 + a] = d[a];
+  }
+  out[6] = p.near;
+  out[7] = p.far;
+  const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // render(): viewdirs (:350)
+#pragma unroll
+  for (int a = 0; a < 3; ++a) out[8 + a] = d[a] / nrm;
+  const float* px3 = images + 3 * (((size_t)img * p.H + py) * p.W + px);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) tgt[a] = px3[a];
+}
+
+// One ordered pool draw (hn_sample_pool_ordered)
+struct PoolOrderK {
+  hn_ray_pool p;
+  const float* images;
+  const float* poses;
+  const int32_t* ids;
+  int64_t start;
+  int n;             // rays, 1 .. HN_POOL_ORDER_MAX
+  int padded;        // n rounded up to a power of two
+  int half;          // the Feistel network's half width (bits)
+  float box_min[3], box_max[3];
+  float* rays;       // [n][11]
+  float* target;     // [n][3]
+  uint32_t* keys;    // [n] or nullptr
+};
+
+// The 30-bit Morton key of a ray's mid-depth point, clamped to the box; every
+// operation a float32 one (the library is built with -ffp-contract=off).
+HN_DEV uint32_t spread_bits10(uint32_t v) {   // bit k -> bit 3k
+  v &= 0x3ffu;
+  v = (v | (v << 16)) & 0x030000ffu;
+  v = (v | (v << 8)) & 0x0300f00fu;
+  v = (v | (v << 4)) & 0x030c30c3u;
+  v = (v | (v << 2)) & 0x09249249u;
+  return v;
+}
+HN_DEV uint32_t pool_key(const PoolOrderK& k, const float* r) {
+  const float tm = 0.5f * (k.p.near + k.p.far);
+  uint32_t key = 0;
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float pt = r[a] + r[3 + a] * tm;
+    float u = (pt - k.box_min[a]) / (k.box_max[a] - k.box_min[a]);
+    u = fminf(fmaxf(u, 0.f), 1.f);   // fmaxf(NaN, 0) = 0
+    const int c = min((int)(u * 1024.f), 1023);
+    key |= spread_bits10((uint32_t)c) << a;
+  }
+  return key;
+}
+
+// The whole draw, by ONE workgroup of exactly kMortonThreads: keys, a bitonic
+// sort of key << 13 | i in LDS (all words distinct, so the network's result is
+// the unique ascending (key, i) order), then the rays of the sorted positions.
+// A compare-exchange stage of stride j gives thread t the pair (lo, lo | j),
+// lo = t with a zero inserted at bit log2 j: for j >= 32 the 32 lanes of a
+// half-wave read 32 consecutive 8-byte words, one 256-byte bank row, without a
+// conflict; for j < 32 they span two rows, a 2-way conflict -- 5 of the 13
+// strides.  The layout stays linear: what the sort costs is a pass over the
+// array per stage (DESIGN 4.6 has the phase times and what was tried).
+constexpr int kPoolIdxBits = 13;
+static_assert((1 << kPoolIdxBits) == HN_POOL_ORDER_MAX, "key << 13 | i holds every position of a batch");
+HN_DEV void pool_order_block(const PoolOrderK& k) {
+  __shared__ uint64_t w[HN_POOL_ORDER_MAX];
+  const int tid = threadIdx.x;
+  for (int i = tid; i < k.padded; i += kMortonThreads) {
+    uint64_t word = ~0ull;   // the padding sorts behind every ray
+    if (i < k.n) {
+      float r[11], t[3];
+      pool_ray(k.p, k.images, k.poses, k.ids, k.half, (uint32_t)(k.start + i), r, t);
+      word = ((uint64_t)pool_key(k, r) << kPoolIdxBits) | (uint64_t)i;
+    }
+    w[i] = word;
+  }
+  __syncthreads();
+  for (int len = 2; len <= k.padded; len <<= 1) {
+    for (int j = len >> 1; j > 0; j >>= 1) {
+      for (int t = tid; t < (k.padded >> 1); t += kMortonThreads) {
+        const int lo = ((t & ~(j - 1)) << 1) | (t & (j - 1)), hi = lo | j;
+        const uint64_t a = w[lo], b = w[hi];
+        if ((a > b) == ((lo & len) == 0)) {
+          w[lo] = b;
+          w[hi] = a;
+        }
+      }
+      __syncthreads();
+    }
+  }
+  for (int j = tid; j < k.n; j += kMortonThreads) {
+    const uint64_t word = w[j];
+    const uint32_t i = (uint32_t)word & (uint32_t)(HN_POOL_ORDER_MAX - 1);
+    pool_ray(k.p, k.images, k.poses, k.ids, k.half, (uint32_t)(k.start + i), k.rays + 11 * (size_t)j,
+             k.target + 3 * (size_t)j);
+    if (k.keys) k.keys[j] = (uint32_t)(word >> kPoolIdxBits);
+  }
+}
+
+// ---------------------------------------------------------------------------
 // Host side: a draw's geometry and checks, shared by hn_sample_batch_morton
 // and hn_render_bwd's next-batch job (which validates before it queues
 // anything).

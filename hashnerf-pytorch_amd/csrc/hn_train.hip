@@ -90,36 +90,17 @@ __global__ __launch_bounds__(256) void sample_pool_kernel(hn_ray_pool p, const f
                                                           float* __restrict__ target) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  const uint32_t hw = (uint32_t)p.H * (uint32_t)p.W;
-  const uint32_t N = (uint32_t)p.n_images * hw;
-  uint32_t x = (uint32_t)(start + i);
-  do {
-    x = feistel(x, half, p.seed);
-  } while (x >= N);
-  const int img = ids[x / hw];
-  const uint32_t pix = x % hw;
-  const int py = (int)(pix / (uint32_t)p.W), px = (int)(pix % (uint32_t)p.W);
-  const float* c = poses + (size_t)img * p.pose_stride;
-  // dirs = [(i - K[0][2]) / K[0][0], -(j - K[1][2]) / K[1][1], -1] (float64: K is)
-  const double d0 = ((double)px - p.cx) / p.fx;
-  const double d1 = -((double)py - p.cy) / p.fy;
-  const double d2 = -1.0;
-  float* out = rays + 11 * i;
-  float d[3];
-#pragma unroll
-  for (int a = 0; a < 3; ++a) {   // np.sum(dirs[..., None, :] * c2w[:3, :3], -1): ((p0 + p1) + p2)
-    d[a] = (float)((d0 * (double)c[4 * a] + d1 * (double)c[4 * a + 1]) + d2 * (double)c[4 * a + 2]);
-    out[a] = c[4 * a + 3];
-    out[3 + a] = d[a];
-  }
-  out[6] = p.near;
-  out[7] = p.far;
-  const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);   // render(): viewdirs (:350)
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[8 + a] = d[a] / nrm;
-  const float* px3 = images + 3 * (((size_t)img * p.H + py) * p.W + px);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) target[3 * i + a] = px3[a];
+  pool_ray(p, images, poses, ids, half, (uint32_t)(start + i), rays + 11 * i, target + 3 * i);
+}
+
+// The batch in Morton order of its rays' mid-depth points (the body in
+// hn_sampler.h): workgroup 0 sorts and emits, the others make the step's
+// uniform draws, as morton_count_kernel places them behind its own.
+__global__ __launch_bounds__(kMortonThreads) void sample_pool_ordered_kernel(PoolOrderK k, UniK u) {
+  if (blockIdx.x >= 1)
+    uniform_block<kMortonThreads>(u, blockIdx.x - 1);
+  else
+    pool_order_block(k);
 }
 
 // ---------------------------------------------------------------------------
@@ -355,6 +336,49 @@ extern "C" int32_t hn_sample_pool(const hn_ray_pool* p, const float* images, con
   const unsigned blocks = (unsigned)((n_rays + 255) / 256);
   hipLaunchKernelGGL(sample_pool_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, images, poses,
                      image_ids, start, n_rays, bits / 2, rays, target);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* images, const float* poses,
+                                          const int32_t* image_ids, int64_t start, int64_t n_rays,
+                                          const float* box_min, const float* box_max, float* rays, float* target,
+                                          uint32_t* keys, uint64_t seed, const hn_uniform_draw* draws,
+                                          int32_t n_draws, void* stream) {
+  // hn_sample_pool's checks, in its order
+  if (!p) return HN_E_NULL;
+  if (n_rays < 0 || start < 0) return HN_E_SHAPE;
+  if (n_rays == 0) return HN_OK;
+  if (!images || !poses || !image_ids || !rays || !target) return HN_E_NULL;
+  if (p->n_images <= 0 || p->H <= 0 || p->W <= 0 || p->pose_stride < 12) return HN_E_SHAPE;
+  const uint64_t N = (uint64_t)p->n_images * (uint64_t)p->H * (uint64_t)p->W;
+  if (N > (1ull << 30) || (uint64_t)start + (uint64_t)n_rays > N) return HN_E_SHAPE;   // one epoch's positions
+  if (n_rays > HN_POOL_ORDER_MAX) return HN_E_SHAPE;   // one workgroup's LDS holds the batch
+  if (!box_min || !box_max) return HN_E_NULL;
+  PoolOrderK k;
+  for (int a = 0; a < 3; ++a) {
+    if (!std::isfinite(box_min[a]) || !std::isfinite(box_max[a]) || !(box_max[a] > box_min[a])) return HN_E_SHAPE;
+    k.box_min[a] = box_min[a];
+    k.box_max[a] = box_max[a];
+  }
+  UniK u;
+  const int32_t st = make_uni(seed, draws, n_draws, u);
+  if (st) return st;
+  int bits = 2;
+  while ((1ull << bits) < N) bits += 2;
+  k.p = *p;
+  k.images = images;
+  k.poses = poses;
+  k.ids = image_ids;
+  k.start = start;
+  k.n = (int)n_rays;
+  k.padded = 1;
+  while (k.padded < k.n) k.padded <<= 1;
+  k.half = bits / 2;
+  k.rays = rays;
+  k.target = target;
+  k.keys = keys;
+  hipLaunchKernelGGL(sample_pool_ordered_kernel, dim3(1 + uni_blocks(u)), dim3(kMortonThreads), 0,
+                     (hipStream_t)stream, k, u);
   return hip_status(hipGetLastError());
 }
 

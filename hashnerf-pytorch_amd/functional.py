@@ -675,12 +675,31 @@ def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=
     return rays, target
 
 
-def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays):
+POOL_ORDER_MAX = L.POOL_ORDER_MAX
+
+
+def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays, order=0, box=None, uniforms=None,
+                return_keys=False):
     """use_batching draw (run_nerf.py:505-521, 544-555): pool positions
     [start, start + n_rays) of the epoch whose shuffle key is `seed`, as the
     [n, 11] ray batch and [n, 3] targets (hn_sample_pool).  images [N, H, W, 3]
     and poses [N, 3|4, 4] on the device; image_ids the training image indices
-    (device int32); K the 3x3 intrinsics (host numbers, used in float64)."""
+    (device int32); K the 3x3 intrinsics (host numbers, used in float64).
+    order=1 (hn_sample_pool_ordered; at most POOL_ORDER_MAX rays) lists the
+    same rays, bitwise, in Morton order of their mid-depth points inside
+    box = (min, max), the hash grid's box; positions with equal keys keep the
+    shuffle's order.  uniforms: shapes of torch.rand draws to make as well
+    (with order=1 in the same launch, else torch_uniform), returned after rays
+    and target; return_keys (order=1) appends the rows' int32 keys."""
+    if order not in (0, 1):
+        raise ValueError(f"sample_pool: order {order!r}")
+    if order == 0 and return_keys:
+        raise ValueError("sample_pool: return_keys needs order=1")
+    if order == 1:
+        if box is None:
+            raise ValueError("sample_pool(order=1) needs box=(min, max), the hash grid's box")
+        if n_rays > L.POOL_ORDER_MAX:
+            raise ValueError(f"sample_pool(order=1): {n_rays} rays, at most {L.POOL_ORDER_MAX} per call")
     L.require_device(images, poses)
     images, poses = images.contiguous(), poses.contiguous()
     if image_ids.dtype != torch.int32 or not image_ids.is_cuda:
@@ -695,8 +714,20 @@ def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays):
     dev = images.device
     rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
     target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
-    L.check(L.lib().hn_sample_pool(p, L.ptr(images), L.ptr(poses), L.ptr(image_ids.contiguous()), int(start),
+    ids = image_ids.contiguous()
+    if order == 1:
+        bmin = (C.c_float * 3)(*(float(v) for v in box[0]))
+        bmax = (C.c_float * 3)(*(float(v) for v in box[1]))
+        keys = torch.empty((n_rays,), dtype=torch.int32, device=dev) if return_keys else None
+        useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
+        L.check(L.lib().hn_sample_pool_ordered(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start), int(n_rays),
+                                               bmin, bmax, L.ptr(rays), L.ptr(target), L.ptr(keys), useed, arr,
+                                               len(outs), L.stream(dev)), "sample_pool_ordered")
+        return (rays, target, *outs, keys) if return_keys else (rays, target, *outs)
+    L.check(L.lib().hn_sample_pool(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
                                    int(n_rays), L.ptr(rays), L.ptr(target), L.stream(dev)), "sample_pool")
+    if uniforms:
+        return (rays, target, *torch_uniform(uniforms, dev))
     return rays, target
 
 

@@ -520,13 +520,21 @@ class Trainer:
     sums), the op-for-op rendition of run_nerf.py."""
 
     def __init__(self, args, data: SyntheticBlender, device, rank=0, world=1, seed=0, mode="explicit",
-                 ray_order=1):
+                 ray_order=1, pool_order=0):
         self.args, self.data, self.device = args, data, torch.device(device)
         self.rank, self.world = rank, world
         if mode not in ("explicit", "autograd", "eager"):
             raise ValueError(f"Trainer mode {mode!r}")
         self.seed, self.mode = seed, mode
         self.ray_order = ray_order   # functional.sample_rays order: 1 Morton (default), 0 draw order
+        # functional.sample_pool order (use_batching): 0 the shuffle's order
+        # (default), 1 each batch in Morton order of its rays' mid-depth points
+        # in the hash grid's box, the step's uniforms drawn in the same launch
+        if pool_order not in (0, 1):
+            raise ValueError(f"Trainer pool_order {pool_order!r}")
+        if pool_order == 1 and not getattr(args, "no_batching", True) and args.N_rand > HF.POOL_ORDER_MAX:
+            raise ValueError(f"Trainer(pool_order=1): N_rand {args.N_rand} per rank, at most {HF.POOL_ORDER_MAX}")
+        self.pool_order = pool_order
         args.bounding_box = data.bounding_box
         torch.manual_seed(seed)                      # identical init on every rank
         (self.kw_train, self.kw_test, self.start, self.grad_vars,
@@ -643,25 +651,36 @@ class Trainer:
         d = self.data
         return int(d.i_train[int(torch.randint(len(d.i_train), (1,), generator=self.cpu_gen))])
 
-    def _pool_draw(self):
+    def _pool_draw(self, uniforms=None):
         """The next use_batching batch (run_nerf.py:544-555): pool positions
         [i_batch, i_batch + N_rand) of this epoch's shuffle -- with world > 1
         the global batch of world * N_rand positions, rank r taking its share --
         then i_batch advances and wraps (new epoch, new shuffle key) once the
         pool is used up.  The last batch of an epoch is short, as the
-        reference's slice."""
+        reference's slice.  pool_order=1: this rank's share in Morton order of
+        its rays' mid-depth points in the embedder's box, and the uniforms
+        ([share, n] for each n) drawn in the same launch."""
         a, d = self.args, self.data
         gB = a.N_rand * self.world
         rem = min(gB, self._pool_n - self.i_batch)
         lo = self.i_batch + rem * self.rank // self.world
         hi = self.i_batch + rem * (self.rank + 1) // self.world
-        rays, target = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, 2., 6.,
-                                      _step_seed(self.seed, 0, -1 - self.epoch), lo, hi - lo)
+        if self.pool_order == 1:
+            g = self.embed_fn.grid()
+            out = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, 2., 6.,
+                                 _step_seed(self.seed, 0, -1 - self.epoch), lo, hi - lo, order=1,
+                                 box=(list(g.box_min), list(g.box_max)),
+                                 uniforms=[(hi - lo, n) for n in uniforms] if uniforms else None)
+        else:
+            out = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, 2., 6.,
+                                 _step_seed(self.seed, 0, -1 - self.epoch), lo, hi - lo)
+            if uniforms:
+                out = (*out, *HF.torch_uniform([(hi - lo, n) for n in uniforms], self.device))
         self.i_batch += gB
         if self.i_batch >= self._pool_n:
             self.epoch += 1
             self.i_batch = 0
-        return rays, target
+        return out
 
     def _draw_rays(self, i: int, uniforms=None):
         """The step's rays and targets: the shuffled pool (use_batching) or
@@ -671,11 +690,7 @@ class Trainer:
         torch's: functional.torch_uniform, inside the sampler's launch),
         returned after rays and target."""
         if self.use_batching:
-            rays, target = self._pool_draw()
-            if uniforms:
-                B = rays.shape[0]
-                return (rays, target, *HF.torch_uniform([(B, n) for n in uniforms], self.device))
-            return rays, target
+            return self._pool_draw(uniforms)
         a, d = self.args, self.data
         img_i = self._train_image()
         crop = self.crop if i < a.precrop_iters else (0, 0, d.H, d.W)

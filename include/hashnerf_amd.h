@@ -457,6 +457,27 @@ typedef struct hn_ray_pool {
  * c2w, pose_stride floats apart); image_ids: device int32 [n_images] (i_train). */
 int32_t hn_sample_pool(const hn_ray_pool* p, const float* images, const float* poses, const int32_t* image_ids,
                        int64_t start, int64_t n_rays, float* rays, float* target, void* stream);
+/* The same batch -- pool positions [start, start + n_rays), every ray's 14
+ * floats bitwise hn_sample_pool's -- listed in Morton order of the rays'
+ * mid-depth points in the hash grid's box, so consecutive rays of the batch
+ * are spatial neighbours as the per-image Morton sampler's are (a pool batch
+ * comes from every training image, so pixel order cannot do it).  Position i
+ * gets the 30-bit key of its float32 o = rays[i][0:3], d = rays[i][3:6] (every
+ * operation a separately rounded float32 one):
+ *   tm = 0.5f * (near + far);  pt_a = o[a] + d[a] * tm
+ *   u_a = fminf(fmaxf((pt_a - box_min[a]) / (box_max[a] - box_min[a]), 0), 1)   (NaN -> 0)
+ *   c_a = min((int)(u_a * 1024), 1023);  key bit 3k + a = bit k of c_a  (a = 0: x, k = 0..9)
+ * and the rows are written in ascending (key, i): ties keep the shuffle's
+ * order.  keys (device [n_rays], or NULL) receives each output row's key.
+ * One launch, no workspace: one workgroup sorts the batch in LDS (so n_rays <=
+ * HN_POOL_ORDER_MAX), further workgroups make the `draws` -- the values of
+ * hn_uniform_philox(seed, draws, n_draws) bitwise.  box_min / box_max: host
+ * float[3], read at call time.  n_rays == 0 is a no-op without a launch. */
+#define HN_POOL_ORDER_MAX 8192
+int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* images, const float* poses,
+                               const int32_t* image_ids, int64_t start, int64_t n_rays, const float* box_min,
+                               const float* box_max, float* rays, float* target, uint32_t* keys, uint64_t seed,
+                               const hn_uniform_draw* draws, int32_t n_draws, void* stream);
 
 /* Blender image preparation (load/load_blender.py:63, :78-86; run_nerf.py:259-262):
  * rgba: device uint8 [n][H][W][4] (the PNGs) -> out, float32:
