@@ -64,6 +64,17 @@ class HnRenderFwdArgs(C.Structure):
                 ("loss", C.POINTER(HnRenderLoss))]
 
 
+class HnImageArgs(C.Structure):
+    _fields_ = [("n_views", C.c_int32), ("H", C.c_int32), ("W", C.c_int32), ("pose_stride", C.c_int32),
+                ("fx", C.c_float), ("fy", C.c_float), ("cx", C.c_float), ("cy", C.c_float),
+                ("near", C.c_float), ("far", C.c_float), ("poses", _P), ("t_vals", _P), ("u", _P), ("table", _P),
+                ("coarse", HnMlp), ("fine", HnMlp), ("rgb", _P), ("depth", _P), ("acc", _P), ("rays", _P),
+                ("weights_packed", C.c_int32)]
+
+
+IMAGE_VARIANTS = {"reencode": 1, "row_major": 2}    # hn_render_image_variant's bits
+
+
 class HnRadamTensor(C.Structure):
     _fields_ = [("p", _P), ("g", _P), ("m", _P), ("v", _P), ("n", C.c_int64),
                 ("beta1", C.c_float), ("beta2", C.c_float), ("one_minus_beta1", C.c_float),
@@ -166,6 +177,10 @@ SIGNATURES = {
                                   C.c_size_t, _P]),
     "hn_render_bwd": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                   C.c_size_t, _P]),
+    "hn_render_image_workspace_bytes": (C.c_size_t, [C.POINTER(HnRenderCfg)]),
+    "hn_render_image": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), _P, C.c_size_t, _P]),
+    "hn_render_image_variant": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), C.c_int32, _P,
+                                            C.c_size_t, _P]),
     "hn_render_bins": (C.c_int32, [C.POINTER(HnRenderCfg), C.c_int64, C.POINTER(C.c_int32)]),
     "hn_render_bwd_owner": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                         C.c_size_t, C.c_int32, C.c_int32, _P]),

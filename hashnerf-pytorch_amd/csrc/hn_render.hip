@@ -2,10 +2,12 @@
 // training ray batch: the C entry points hn_render_fwd / hn_render_bwd, the
 // pre-pass kernel of both backward schedules (not launched by the binned one
 // after a training forward that did its work, hn_render_fwd_args.loss), and
-// the host side.  One
+// the host side; and hn_render_image, the evaluation renderer (whole images
+// from poses, hn_render_image.h).  One
 // translation unit; the device code is in the headers (each says what it holds).
 #include "hn_render_args.h"   // kernel arguments, rays, feature cache, shared helpers
 #include "hn_render_fwd.h"    // render_fwd_kernel
+#include "hn_render_image.h"  // render_image_kernel: whole images from poses, nothing saved
 #include "hn_mlp_bwd.h"       // one tile's MLP backward, dW slabs, render_bwd_kernel's declaration
 #include "hn_bwd_binned.h"    // binned schedule: render_bwd_kernel<kSwVmcnt, kModeSplit>, records, owner pass
 #include "hn_bwd_atomic.h"    // float-atomic fused schedule: render_bwd_kernel<CAP, kModeAtomic>
@@ -386,6 +388,59 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
     hipLaunchKernelGGL(render_fwd_kernel<false>, dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
   }
   return hip_status(hipGetLastError());
+}
+
+// Workspace of hn_render_image: both nets' packed weights | one slot per wave of
+// the persistent grid (its current ray's two coarse feature tiles)
+static size_t image_ws_floats() { return (size_t)2 * G_END + (size_t)kImgBlocks * kFwdBlockWaves * kImgSlotFloats; }
+
+extern "C" size_t hn_render_image_workspace_bytes(const hn_render_cfg* cfg) {
+  return check_cfg(cfg) ? 0 : image_ws_floats() * sizeof(float);
+}
+
+extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
+                                           void* workspace, size_t ws_bytes, void* stream) {
+  int32_t st = check_cfg(cfg);
+  if (st) return st;
+  if (!a) return HN_E_NULL;
+  if (cfg->perturb) return HN_E_SHAPE;   // the stratified jitter is the training forward's
+  if (a->H <= 0 || a->W <= 0 || a->n_views < 0 || (a->pose_stride != 12 && a->pose_stride != 16)) return HN_E_SHAPE;
+  if (variant < 0 || variant > (kImgReencode | kImgRowMajor)) return HN_E_SHAPE;
+  if (a->n_views == 0) return HN_OK;
+  if (!a->poses || !a->t_vals || !a->u || !a->table || !mlp_ok(a->coarse) || !mlp_ok(a->fine)) return HN_E_NULL;
+  if (!a->rgb || !a->depth || !a->acc) return HN_E_NULL;
+  if (!workspace) return HN_E_NULL;
+  if (ws_bytes < image_ws_floats() * sizeof(float)) return HN_E_WORKSPACE;
+  ImageK k;
+  k.Hb = ((uint32_t)a->H + 1) / 2;
+  k.Wb = ((uint32_t)a->W + 1) / 2;
+  // the ray groups' index is 32 bits wide (an 8-view batch of 16384 x 16384 images still fits)
+  if ((uint64_t)a->H * (uint64_t)a->W > 0x7fffffffull) return HN_E_SHAPE;
+  const uint64_t groups = (variant & kImgRowMajor) ? ((uint64_t)a->n_views * a->H * a->W + 3) / 4
+                                                   : (uint64_t)a->n_views * k.Hb * k.Wb;
+  if (groups > 0x7fffffffull) return HN_E_SHAPE;
+  hipStream_t s = (hipStream_t)stream;
+  float* Pc = (float*)workspace;
+  float* Pf = Pc + G_END;
+  if (!a->weights_packed && (st = mlp_pack2_launch(&a->coarse, Pc, &a->fine, Pf, s))) return st;
+  k.g = make_grid_args(cfg->grid);
+  k.white = cfg->white_bkgd;
+  k.lindisp = cfg->lindisp;
+  k.variant = variant;
+  k.n_views = a->n_views; k.H = a->H; k.W = a->W; k.pose_stride = a->pose_stride;
+  k.groups = (uint32_t)groups;
+  k.fx = a->fx; k.fy = a->fy; k.cx = a->cx; k.cy = a->cy; k.near = a->near; k.far = a->far;
+  k.poses = a->poses; k.tvals = a->t_vals; k.u = a->u; k.table = a->table;
+  k.Pc = Pc; k.Pf = Pf;
+  k.slots = (variant & kImgReencode) ? nullptr : Pf + G_END;
+  k.rgb = a->rgb; k.depth = a->depth; k.acc = a->acc; k.rays = a->rays;
+  hipLaunchKernelGGL(render_image_kernel, dim3(kImgBlocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_render_image(const hn_render_cfg* cfg, const hn_image_args* a, void* workspace,
+                                   size_t ws_bytes, void* stream) {
+  return hn_render_image_variant(cfg, a, 0, workspace, ws_bytes, stream);
 }
 
 extern "C" int32_t hn_render_bins(const hn_render_cfg* cfg, int64_t n_rays, int32_t* shift) {

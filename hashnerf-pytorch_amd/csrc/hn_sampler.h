@@ -113,15 +113,16 @@ HN_DEV void morton_count_block(const MortonK& k, unsigned b) {
   if (threadIdx.x == 0) k.counts[b] = c;
 }
 
-HN_DEV void emit_ray(const hn_ray_sampler& s, const float* __restrict__ image, const float* __restrict__ c2w,
-                     uint32_t x, int64_t r, float* __restrict__ rays, float* __restrict__ target) {
-  const int py = s.crop_y0 + (int)(x / (uint32_t)s.crop_w);
-  const int px = s.crop_x0 + (int)(x % (uint32_t)s.crop_w);
+// The ray of pixel (row py, column px) as render() packs it
+// (ray_util.py:62-80, run_nerf_helpers.py:355-368): out[11] = [o3 d3 near far
+// viewdir3].  Every ray a sampler or the image renderer makes comes from here,
+// float32 operation for float32 operation.
+HN_DEV void pixel_ray(float fx, float fy, float cx, float cy, float near, float far, const float* __restrict__ c2w,
+                      int px, int py, float out[11]) {
   // dirs = [(i - cx) / fx, -(j - cy) / fy, -1]; rays_d = sum(dirs * c2w[:3,:3], -1)
-  const float d0 = ((float)px - s.cx) / s.fx;
-  const float d1 = -(((float)py - s.cy) / s.fy);
+  const float d0 = ((float)px - cx) / fx;
+  const float d1 = -(((float)py - cy) / fy);
   const float d2 = -1.f;
-  float* out = rays + 11 * r;
   float d[3];
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
@@ -129,11 +130,21 @@ HN_DEV void emit_ray(const hn_ray_sampler& s, const float* __restrict__ image, c
     out[a] = c2w[4 * a + 3];
     out[3 + a] = d[a];
   }
-  out[6] = s.near;
-  out[7] = s.far;
+  out[6] = near;
+  out[7] = far;
   const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
 #pragma unroll
   for (int a = 0; a < 3; ++a) out[8 + a] = d[a] / nrm;
+}
+
+HN_DEV void emit_ray(const hn_ray_sampler& s, const float* __restrict__ image, const float* __restrict__ c2w,
+                     uint32_t x, int64_t r, float* __restrict__ rays, float* __restrict__ target) {
+  const int py = s.crop_y0 + (int)(x / (uint32_t)s.crop_w);
+  const int px = s.crop_x0 + (int)(x % (uint32_t)s.crop_w);
+  float ray[11];
+  pixel_ray(s.fx, s.fy, s.cx, s.cy, s.near, s.far, c2w, px, py, ray);
+#pragma unroll
+  for (int a = 0; a < 11; ++a) rays[11 * r + a] = ray[a];
   const float* px3 = image + 3 * ((size_t)py * s.W + px);
 #pragma unroll
   for (int a = 0; a < 3; ++a) target[3 * r + a] = px3[a];

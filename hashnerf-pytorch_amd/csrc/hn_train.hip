@@ -31,23 +31,10 @@ __global__ __launch_bounds__(256) void sample_rays_kernel(hn_ray_sampler s, cons
   } while (x >= M);
   const int py = s.crop_y0 + (int)(x / (uint32_t)s.crop_w);
   const int px = s.crop_x0 + (int)(x % (uint32_t)s.crop_w);
-  // dirs = [(i - cx) / fx, -(j - cy) / fy, -1]; rays_d = sum(dirs * c2w[:3,:3], -1)
-  const float d0 = ((float)px - s.cx) / s.fx;
-  const float d1 = -(((float)py - s.cy) / s.fy);
-  const float d2 = -1.f;
-  float* out = rays + 11 * i;
-  float d[3];
+  float ray[11];
+  pixel_ray(s.fx, s.fy, s.cx, s.cy, s.near, s.far, c2w, px, py, ray);
 #pragma unroll
-  for (int a = 0; a < 3; ++a) {
-    d[a] = d0 * c2w[4 * a] + d1 * c2w[4 * a + 1] + d2 * c2w[4 * a + 2];
-    out[a] = c2w[4 * a + 3];
-    out[3 + a] = d[a];
-  }
-  out[6] = s.near;
-  out[7] = s.far;
-  const float nrm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
-#pragma unroll
-  for (int a = 0; a < 3; ++a) out[8 + a] = d[a] / nrm;
+  for (int a = 0; a < 11; ++a) rays[11 * i + a] = ray[a];
   const float* px3 = image + 3 * ((size_t)py * s.W + px);
 #pragma unroll
   for (int a = 0; a < 3; ++a) target[3 * i + a] = px3[a];

@@ -968,6 +968,74 @@ def make_render_cfg(grid: L.HnGrid, white_bkgd: bool, lindisp: bool, perturb: bo
     return c
 
 
+def render_image(cfg, H, W, K, poses, near, far, table, ws, t_vals=None, u=None, wsb=None, weights_packed=False,
+                 return_rays=False, variant=0, out=None):
+    """hn_render_image (run_nerf_helpers.py:310-392 under :395-459): every
+    pose of ``poses`` ([n, 3, 4] or [n, 4, 4] c2w on the device) rendered in
+    one launch as render(H, W, K, c2w=pose, ndc=False, use_viewdirs=True) with
+    perturb = 0 and raw_noise_std = 0 renders it.  Returns (rgb [n, H, W, 3],
+    depth [n, H, W], acc [n, H, W]) and, with return_rays, the [n H W, 11] ray
+    batch the kernel made, in pixel order.  cfg: make_render_cfg(..., perturb=
+    False); ws: the coarse then the fine net's five weights; t_vals / u: by
+    default the tensors render_rays uses (linspace(0, 1, 64) made on the CPU,
+    linspace(0, 1, 128) on the device).  wsb: the caller's workspace (uint8, >=
+    hn_render_image_workspace_bytes; its size does not depend on the images);
+    weights_packed: it already holds ws's packed copies.  variant: the
+    measured design alternatives (L.IMAGE_VARIANTS' bits; bitwise the same
+    images).  out: (rgb, depth, acc) to write into instead of fresh tensors."""
+    L.require_device(poses, table, t_vals, u, *ws)
+    dev = poses.device
+    if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"hashnerf_amd.render_image: poses must be [n, 3, 4] or [n, 4, 4], got {tuple(poses.shape)}")
+    poses = poses.contiguous()
+    n = poses.shape[0]
+    if t_vals is None:
+        from .render import _linspace_cached
+        t_vals = _linspace_cached(64, dev)
+    if u is None:
+        u = torch.linspace(0., 1., 128, device=dev)
+    t_vals, u, table = t_vals.contiguous(), u.contiguous(), table.contiguous()
+    if t_vals.numel() != 64 or u.numel() != 128:
+        raise ValueError("hashnerf_amd.render_image: t_vals must hold 64 and u 128 values")
+    ws = [w.contiguous() for w in ws]
+    H, W = int(H), int(W)
+    if out is None:
+        out = (torch.empty((n, H, W, 3), dtype=torch.float32, device=dev),
+               torch.empty((n, H, W), dtype=torch.float32, device=dev),
+               torch.empty((n, H, W), dtype=torch.float32, device=dev))
+    rgb, depth, acc = out
+    L.require_device(rgb, depth, acc)
+    for t, shape in ((rgb, (n, H, W, 3)), (depth, (n, H, W)), (acc, (n, H, W))):
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"hashnerf_amd.render_image: out tensors must be contiguous {shape} on {dev}")
+    rays = torch.empty((n * H * W, 11), dtype=torch.float32, device=dev) if return_rays else None
+    a = L.HnImageArgs()
+    a.n_views, a.H, a.W, a.pose_stride = n, H, W, poses.shape[1] * 4
+    a.fx, a.fy, a.cx, a.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+    a.near, a.far = float(near), float(far)
+    for k, t in (("poses", poses), ("t_vals", t_vals), ("u", u), ("table", table), ("rgb", rgb), ("depth", depth),
+                 ("acc", acc), ("rays", rays)):
+        setattr(a, k, None if t is None else t.data_ptr())
+    a.coarse = L.make_mlp(ws[:5])
+    a.fine = L.make_mlp(ws[5:])
+    a.weights_packed = 1 if weights_packed else 0
+    nbytes = L.lib().hn_render_image_workspace_bytes(cfg)
+    if wsb is None:
+        wsb = _ws(nbytes, dev)
+    elif wsb.numel() * wsb.element_size() < nbytes or not wsb.is_contiguous() or wsb.device != dev:
+        raise ValueError(f"hashnerf_amd.render_image: wsb must be a contiguous buffer of >= {nbytes} bytes on {dev}")
+    else:
+        nbytes = wsb.numel() * wsb.element_size()
+    t0 = TIMER.begin("render_image")
+    if variant:
+        L.check(L.lib().hn_render_image_variant(cfg, a, int(variant), L.ptr(wsb), nbytes, L.stream(dev)),
+                "render_image_variant")
+    else:
+        L.check(L.lib().hn_render_image(cfg, a, L.ptr(wsb), nbytes, L.stream(dev)), "render_image")
+    TIMER.end("render_image", t0)
+    return (rgb, depth, acc, rays) if return_rays else (rgb, depth, acc)
+
+
 def render_rays_fused(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table,
                       coarse_ws: Sequence[torch.Tensor], fine_ws: Sequence[torch.Tensor]):
     keep_feat = torch.is_grad_enabled() and any(

@@ -246,22 +246,77 @@ def render_ray_batch(rays_, out_shape, chunk=1024 * 32, **kwargs):
     return [all_ret[k] for k in k_extract] + [{k: all_ret[k] for k in all_ret if k not in k_extract}]
 
 
+def _image_ineligible(kw) -> Optional[str]:
+    """Why render_image cannot render this render() configuration (None: it can)."""
+    if not _fusable(np.empty((0, 11)), kw.get("network_fn"), kw.get("network_query_fn"), kw.get("N_samples"),
+                    kw.get("N_importance", 0), kw.get("network_fine")):
+        return "not the fused HashNeRF configuration (16-level hash grid + SH, two NeRFSmall nets, 64 + 128 samples)"
+    for why, bad in (("perturb != 0", kw.get("perturb", 0.) != 0.),
+                     ("raw_noise_std != 0", kw.get("raw_noise_std", 0.) != 0.),
+                     ("ndc rays", bool(kw.get("ndc", True))),
+                     ("no view directions (use_viewdirs=False)", not kw.get("use_viewdirs", False)),
+                     ("c2w_staticcam", kw.get("c2w_staticcam") is not None),
+                     ("retraw", bool(kw.get("retraw", False)))):
+        if bad:
+            return why
+    return None
+
+
+@torch.no_grad()
+def render_image(H, W, K, c2w, **render_kwargs):
+    """render(H, W, K, c2w=c2w, **render_kwargs)'s rgb, depth and acc maps from
+    the whole-image kernel (functional.render_image): rays, both passes and
+    the composite in one launch, nothing else written.  c2w: one [3, 4] pose or
+    [n, 3, 4] (or [.., 4, 4]) poses, all rendered in that launch; returns rgb
+    [(n,) H, W, 3], depth and acc [(n,) H, W].  Raises ValueError, naming the
+    reason, for a configuration the kernel does not cover: anything but the
+    fused HashNeRF configuration, perturb, raw noise, ndc, no view directions,
+    c2w_staticcam or retraw."""
+    why = _image_ineligible(render_kwargs)
+    if why is not None:
+        raise ValueError(f"hashnerf_amd.render_image: not eligible: {why}")
+    c2w = torch.as_tensor(c2w)
+    L.require_device(c2w)
+    single = c2w.dim() == 2
+    poses = (c2w[None] if single else c2w)[:, :3, :4]
+    kw = render_kwargs
+    emb = kw["network_query_fn"].embed_fn
+    cfg = HF.make_render_cfg(emb.grid(), bool(kw.get("white_bkgd", False)), bool(kw.get("lindisp", False)), False)
+    out = HF.render_image(cfg, H, W, K, poses, kw.get("near", 0.), kw.get("far", 1.), emb.table,
+                          kw["network_fn"].weights() + kw["network_fine"].weights())
+    return tuple(t[0] for t in out) if single else out
+
+
+_IMAGE_GROUP = 8    # views per render_image launch of render_path: bounds the output buffers
+
+
 @torch.no_grad()
 def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedir=None,
-                render_factor=0):
+                render_factor=0, image_kernel=False):
     """run_nerf_helpers.py:395-459 (evaluation): returns (rgbs, depths), depth
     normalised to [0, 1] between near and far.  With gt_imgs (and no
     render_factor) the per-image PSNRs are computed as the reference does and,
     when savedir is given, pickled to test_psnrs_avg{avg:0.2f}.pkl like
     :452-456.  The per-frame matplotlib figures (:435-449) are not written:
-    plotting is outside the hot path."""
+    plotting is outside the hot path.
+    image_kernel=True renders the poses through render_image, _IMAGE_GROUP
+    views per launch, where the configuration is eligible for it (the same
+    maps, PSNRs and pickle); where it is not, this is the default path."""
     H, W, focal = hwf
     near, far = render_kwargs["near"], render_kwargs["far"]
     if render_factor != 0:
         H, W, focal = H // render_factor, W // render_factor, focal / render_factor
     rgbs, depths, psnrs = [], [], []
+    use_image = image_kernel and _image_ineligible(render_kwargs) is None
+    maps = None
     for i, c2w in enumerate(render_poses):
-        rgb, depth, acc, _ = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
+        if use_image:
+            if i % _IMAGE_GROUP == 0:
+                group = torch.stack([torch.as_tensor(p)[:3, :4] for p in render_poses[i:i + _IMAGE_GROUP]], 0)
+                maps = render_image(H, W, K, group, **render_kwargs)
+            rgb, depth = maps[0][i % _IMAGE_GROUP], maps[1][i % _IMAGE_GROUP]
+        else:
+            rgb, depth, acc, _ = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)
         rgbs.append(rgb.cpu().numpy())
         depths.append(((depth - near) / (far - near)).cpu().numpy())
         if gt_imgs is not None and render_factor == 0:

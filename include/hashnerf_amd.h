@@ -27,7 +27,9 @@ extern "C" {
 /* 14 also covers three additive fields appended at the end of their structs,
  * where zero / NULL keeps the earlier behaviour: hn_render_fwd_args.loss,
  * hn_render_bwd_args.prepass_done and .next_batch (a caller built against the shorter structs
- * must zero-fill the args, as every caller of this ABI does). */
+ * must zero-fill the args, as every caller of this ABI does), and the additive
+ * entry points hn_sample_pool_ordered and hn_render_image (with its
+ * hn_render_image_workspace_bytes and hn_render_image_variant). */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
 
@@ -520,6 +522,51 @@ int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
 int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- whole images from poses (additive under ABI 14) ----------------------
+ * The evaluation renderer: run_nerf_helpers.py:310-392 render(H, W, K,
+ * c2w=pose, ndc=False, use_viewdirs=True) with perturb = 0 and raw_noise_std =
+ * 0, for every pose of a list as :395-459 render_path walks it -- one launch,
+ * poses in and images out.  Pixel (row j, column i) of view v gets the ray of
+ * hn_sample_rays for that pixel (ray_util.py:62-80, the normalised view
+ * direction; the same float32 operations in the same order) and
+ * hn_render_fwd's rgb / depth / acc for that ray bit for bit, under the same
+ * hn_render_cfg (white_bkgd and lindisp honoured; perturb != 0 is
+ * HN_E_SHAPE).  Tiles of 32 samples without density skip the colour net, as
+ * hn_render_fwd_args.skip_dead_color (no noise here, so no output changes).
+ * Nothing but the three images is written: no z, raw, coarse outputs,
+ * entropies or features.  A fixed grid of workgroups loops over the rays --
+ * 2 x 2 pixel blocks, 16 x 16 pixel tiles of them in Morton order, view after
+ * view -- so the workspace (both nets' packed weights, and per resident wave
+ * the two coarse feature tiles its ray's fine pass reuses) depends on cfg
+ * only, not on H, W or n_views.
+ * H, W <= 0, n_views < 0, a pose_stride other than 12 or 16, or more than
+ * 2^31 - 1 ray groups (4 rays): HN_E_SHAPE; n_views == 0: HN_OK without a launch. */
+typedef struct hn_image_args {
+  int32_t n_views, H, W;
+  int32_t pose_stride;            /* floats between consecutive c2w matrices (12 or 16) */
+  float fx, fy, cx, cy;           /* K, as hn_ray_sampler */
+  float near, far;
+  const float* poses;             /* device [n_views][3][4] row-major c2w */
+  const float* t_vals;            /* device [64]  torch.linspace(0,1,64) */
+  const float* u;                 /* device [128] the det importance uniforms, the same for every ray */
+  const float* table;
+  hn_mlp coarse, fine;
+  float* rgb;                     /* [n_views][H][W][3] */
+  float* depth; float* acc;       /* [n_views][H][W] */
+  float* rays;                    /* optional [n_views*H*W][11], pixel order (view, row, column); NULL = not written */
+  int32_t weights_packed;         /* as hn_render_fwd_args */
+} hn_image_args;
+size_t  hn_render_image_workspace_bytes(const hn_render_cfg* cfg);
+int32_t hn_render_image(const hn_render_cfg* cfg, const hn_image_args* a, void* workspace, size_t ws_bytes,
+                        void* stream);
+/* The same call with one of the design alternatives it was measured against
+ * (scripts/render_image_ab.py), every output bitwise hn_render_image's:
+ * variant bit 0 = every fine sample hash-encoded (no reuse of the coarse
+ * twins' features), bit 1 = rays taken in (view, row, column) order, 4
+ * consecutive pixels per workgroup.  0 = hn_render_image. */
+int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
+                                void* workspace, size_t ws_bytes, void* stream);
 
 #ifdef __cplusplus
 }
