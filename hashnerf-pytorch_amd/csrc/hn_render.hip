@@ -303,6 +303,18 @@ static void launch_owner(const BinR& r, const BinGeom& bg, int n_bins, hipStream
                      (size_t)(2 << bg.shift) * sizeof(unsigned long long), s, r);
 }
 
+// What hn_render_fwd and hn_render_image share of their kernels' arguments; the
+// nets' packed copies at the head of the workspace are made here unless given
+static int32_t field_args(const hn_render_cfg* cfg, const float* t_vals, const float* u, const float* table,
+                          const hn_mlp& coarse, const hn_mlp& fine, int32_t weights_packed, void* workspace,
+                          hipStream_t s, FieldK& f) {
+  float* Pc = (float*)workspace;
+  float* Pf = Pc + G_END;
+  if (int32_t st = weights_packed ? 0 : mlp_pack2_launch(&coarse, Pc, &fine, Pf, s)) return st;
+  f = FieldK{make_grid_args(cfg->grid), cfg->white_bkgd, cfg->lindisp, t_vals, u, table, Pc, Pf};
+  return HN_OK;
+}
+
 }  // namespace hn
 
 using namespace hn;
@@ -346,18 +358,13 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
     if (plan.mode != kModeSplit) return HN_E_SHAPE;   // only the binned backward can skip its pre-pass
   }
   hipStream_t s = (hipStream_t)stream;
-  float* Pc = (float*)workspace;
-  float* Pf = Pc + G_END;
-  if (!a->weights_packed && (st = mlp_pack2_launch(&a->coarse, Pc, &a->fine, Pf, s))) return st;
   RenderK k;
-  k.g = make_grid_args(cfg->grid);
-  k.white = cfg->white_bkgd;
-  k.lindisp = cfg->lindisp;
+  if ((st = field_args(cfg, a->t_vals, a->u, a->table, a->coarse, a->fine, a->weights_packed, workspace, s, k.f)))
+    return st;
   k.perturb = cfg->perturb;
   k.B = a->n_rays;
-  k.rays = a->rays; k.tvals = a->t_vals; k.t_rand = a->t_rand; k.u = a->u;
-  k.noise_c = a->noise_c; k.noise_f = a->noise_f; k.table = a->table;
-  k.Pc = Pc; k.Pf = Pf;
+  k.rays = a->rays; k.t_rand = a->t_rand;
+  k.noise_c = a->noise_c; k.noise_f = a->noise_f;
   k.rgb = a->rgb; k.depth = a->depth; k.acc = a->acc; k.sparsity = a->sparsity;
   k.rgb0 = a->rgb0; k.depth0 = a->depth0; k.acc0 = a->acc0; k.sparsity0 = a->sparsity0;
   k.z_std = a->z_std; k.z_coarse = a->z_coarse; k.z_fine = a->z_fine;
@@ -420,19 +427,14 @@ extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_im
                                                    : (uint64_t)a->n_views * k.Hb * k.Wb;
   if (groups > 0x7fffffffull) return HN_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  float* Pc = (float*)workspace;
-  float* Pf = Pc + G_END;
-  if (!a->weights_packed && (st = mlp_pack2_launch(&a->coarse, Pc, &a->fine, Pf, s))) return st;
-  k.g = make_grid_args(cfg->grid);
-  k.white = cfg->white_bkgd;
-  k.lindisp = cfg->lindisp;
+  if ((st = field_args(cfg, a->t_vals, a->u, a->table, a->coarse, a->fine, a->weights_packed, workspace, s, k.f)))
+    return st;
   k.variant = variant;
   k.n_views = a->n_views; k.H = a->H; k.W = a->W; k.pose_stride = a->pose_stride;
   k.groups = (uint32_t)groups;
   k.fx = a->fx; k.fy = a->fy; k.cx = a->cx; k.cy = a->cy; k.near = a->near; k.far = a->far;
-  k.poses = a->poses; k.tvals = a->t_vals; k.u = a->u; k.table = a->table;
-  k.Pc = Pc; k.Pf = Pf;
-  k.slots = (variant & kImgReencode) ? nullptr : Pf + G_END;
+  k.poses = a->poses;
+  k.slots = (variant & kImgReencode) ? nullptr : (float*)workspace + 2 * (size_t)G_END;
   k.rgb = a->rgb; k.depth = a->depth; k.acc = a->acc; k.rays = a->rays;
   hipLaunchKernelGGL(render_image_kernel, dim3(kImgBlocks), dim3(64 * kFwdBlockWaves), 0, s, k);
   return hip_status(hipGetLastError());

@@ -1,6 +1,6 @@
 // hn_render_args.h -- what every kernel of hn_render.hip shares: the kernel-
-// argument structs (RenderK, B1K, ScK, BinR), the backward schedules' names,
-// a ray and its points, the saved feature / ReLU-mask cache, encode_tile, and
+// argument structs (FieldK, RenderK, B1K, ScK, BinR), the backward
+// schedules' names, a ray and its points, the saved feature / ReLU-mask cache, encode_tile, and
 // the few device helpers both backward schedules use (DPP row shifts,
 // voxel_cw, the exact-zero test, the sticky device fault word).
 #pragma once
@@ -21,19 +21,23 @@ constexpr int kSc = 64, kNi = 128, kSf = 192;
 constexpr int kFwdWaves = 4;
 constexpr int kBwdBlocks = 256;          // persistent backward: one block per CU
 
-struct RenderK {
+// The field and the sampling: the part RenderK and ImageK share (field_args,
+// hn_render.hip), and what the shared ray passes of hn_render_fwd.h read
+struct FieldK {
   GridArgs g;
-  int white, lindisp, perturb;
-  int64_t B;
-  const float* rays;
+  int white, lindisp;
   const float* tvals;
-  const float* t_rand;
   const float* u;
-  const float* noise_c;
-  const float* noise_f;
   const float* table;
-  const float* Pc;
+  const float* Pc;   // the two nets' packed weights
   const float* Pf;
+};
+
+struct RenderK {
+  FieldK f;
+  int perturb;
+  int64_t B;
+  const float *rays, *t_rand, *noise_c, *noise_f;
   float *rgb, *depth, *acc, *sparsity, *rgb0, *depth0, *acc0, *sparsity0, *z_std;
   float *z_coarse, *z_fine, *raw_c, *raw_f;
   uint8_t* fine_src;
@@ -109,8 +113,8 @@ struct Ray {
   float o[3], d[3], vd[3], near, far, dnorm;
 };
 
-HN_DEV void load_ray(const float* __restrict__ rays, int64_t ray, Ray& r) {
-  const float* rb = rays + 11 * ray;
+// A ray from its 11 floats [o | d | near far | viewdir]
+HN_DEV void make_ray(const float* __restrict__ rb, Ray& r) {
 #pragma unroll
   for (int a = 0; a < 3; ++a) {
     r.o[a] = rb[a];
@@ -121,6 +125,7 @@ HN_DEV void load_ray(const float* __restrict__ rays, int64_t ray, Ray& r) {
   r.far = rb[7];
   r.dnorm = sqrtf(r.d[0] * r.d[0] + r.d[1] * r.d[1] + r.d[2] * r.d[2]);   // torch.norm (:595)
 }
+HN_DEV void load_ray(const float* __restrict__ rays, int64_t ray, Ray& r) { make_ray(rays + 11 * ray, r); }
 
 // pts = rays_o + rays_d * z (:538, :552)
 HN_DEV void ray_point(const Ray& r, float z, float pt[3]) {
@@ -211,13 +216,14 @@ HN_DEV void encode_tile(const GridArgs& g, const float* gsl, const float* __rest
   }
 }
 
-HN_DEV void ray_sh(const Ray& r, int h, float sh8[8], float shx8[8]) {
+// shx8 (the backward's dW_c0 staging) only where it is asked for
+HN_DEV void ray_sh(const Ray& r, int h, float sh8[8], float* shx8 = nullptr) {
   float sh[16];
   sh16(r.vd[0], r.vd[1], r.vd[2], sh);
 #pragma unroll
   for (int s = 0; s < 8; ++s) {
     sh8[s] = h ? sh[2 * s + 1] : sh[2 * s];
-    shx8[s] = h ? sh[8 + s] : sh[s];
+    if (shx8) shx8[s] = h ? sh[8 + s] : sh[s];
   }
 }
 

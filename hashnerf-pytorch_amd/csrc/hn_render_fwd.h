@@ -6,6 +6,12 @@
 // runs (192) -> 6 fine tiles (a coarse sample's features reused) ->
 // composite.  Saves each tile's features and ReLU masks for the backward,
 // except (skip_dead) those of fine tiles without density.
+//
+// The ray passes -- coarse_z, pass_start, pass_tiles (one tile loop, coarse
+// and fine), importance_sort -- are written once here, for this kernel and for
+// render_image_kernel (hn_render_image.h), whose pixels are this forward's bit
+// for bit.  What a kernel does with a tile's results is its compile-time
+// policy (TrainTiles below, ImageTiles there).
 #pragma once
 #include "hn_render_args.h"
 
@@ -36,6 +42,127 @@ constexpr int kFwdWavesPerSimd = 4;
 // 0.301-0.313 ms; profiles/r04/r04e, r04f.)
 constexpr int kFwdBlockWaves = kFwdWaves;
 
+// ---- the ray passes, shared with render_image_kernel -----------------------
+// L: the wave's kFLds floats (the map above), ring: its FragRing slot, gsl: the
+// block's staged grid sizes.  A policy Pol, every hook inline (pass: 0 coarse,
+// 1 fine, a constant at each call):
+//   kMasks           the tiles' ReLU masks are formed
+//   twins()          the ray's two stored coarse tiles (store_feat's layout), or null
+//   origin(q)        fine sample q's coarse sample, or 255 (asked only with twins)
+//   skip_dead(pass)  mlp_fwd_tile_src's skip_dead
+//   save_feat(pass, tau, lane, feat), save_masks(pass, tau, lane, m), save_raw(pass, q, o4): the stores
+
+// coarse z_vals (:514-536) before the jitter
+HN_DEV float coarse_z(float t, float near, float far, int lindisp) {
+  return lindisp ? 1.f / (1.f / near * (1.f - t) + 1.f / far * t) : near * (1.f - t) + far * t;
+}
+
+// A pass's prologue: color_net.0's SH half of the ray into LDS (the previous
+// pass's tiles have read theirs: in-order LDS), the net's first chunk into the
+// ring.  drain: the previous pass's last (unused) ring fill lands first.
+HN_DEV void pass_start(const float* P, const float sh8[8], float* L, float* ring, int lane, bool drain) {
+  c0sh_lds_store(opaque_ptr(P), sh8, L + kFC0, lane);
+  lds_fence_wave();
+  if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+  fwd_ring_start(P, ring, lane);
+}
+
+// The coarse twin src of a fine sample: its features from the ray's stored
+// coarse tiles (4 dwordx4, written by this wave)
+HN_DEV void load_twin_feat(const float* tiles, int src, int h, f32x16& feat) {
+  const f32x4* t = reinterpret_cast<const f32x4*>(tiles + (size_t)(src >> 5) * 1024) + (src & 31) + 32 * h;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const f32x4 v = t[64 * c];
+    feat[4 * c] = v.x; feat[4 * c + 1] = v.y; feat[4 * c + 2] = v.z; feat[4 * c + 3] = v.w;
+  }
+}
+
+// importance sampling (:547-551), then sort(cat(z_vals, z_samples)) (:551): a
+// merge of the sorted coarse run with the bitonic-sorted importance samples
+// (rawb is free until the fine tiles), the all-pairs rank sort if the coarse
+// run is ever out of order (render_fwd_kernel 0.2998 -> 0.2966 ms, r04c).
+// zsrc keeps the samples as drawn; org[i]: sorted sample i's coarse origin.
+HN_DEV void importance_sort(float* L, const float* u, uint8_t* org, int lane) {
+  float* zsrc = L + kFZsrc;
+  lds_fence_wave();
+  sample_pdf_wave(L + kFBins, L + kFW + 1, kSc - 2, L + kFCdf, u, kNi, zsrc + kSc, lane);
+  lds_fence_wave();
+  if (!merge_sort_z(zsrc, L + kFZs, L + kFRaw, lane, org)) rank_sort_wave(zsrc, L + kFZs, kSf, lane, org, kSc);
+}
+
+// A pass's tiles: kPass 0 the coarse network (:540), 2 tiles at zc; 1 the fine
+// network (:556), 6 tiles at zs
+template <int kPass, class Pol>
+HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L, const Ray& r, int lane, Pol& pol) {
+  const int p = lane & 31, h = lane >> 5;
+  for (int tau = 0; tau < (kPass ? kSf : kSc) / 32; ++tau) {
+    const float* P = opaque_ptr(kPass ? f.Pf : f.Pc);
+    const int q = 32 * tau + p;
+    float pt[3];
+    ray_point(r, L[(kPass ? kFZs : kFZc) + q], pt);
+    f32x16 feat;
+    // a third of the fine samples are the coarse samples again (the merge
+    // keeps their z bitwise): with the coarse tiles stored, those lanes load
+    // the coarse tile's features instead of gathering 16 levels x 8 corners
+    // again -- a quarter of the ray's gathers (render_fwd_kernel 0.282 ->
+    // 0.275 ms, r04h).  Encoding only the 128 importance samples as 4 full
+    // tiles first and loading every fine tile's features back from the cache
+    // (a third fewer encode instructions) measured slower: 0.301 ms, the
+    // waves then run their MLP tiles in step (r04j).
+    const float* twins = kPass ? pol.twins() : nullptr;
+    const int src = twins ? pol.origin(q) : 255;
+    if (src >= kSc) {
+      HN_FWD_PRIO_HI();
+      encode_tile(f.g, gsl, f.table, pt, h, feat);
+      HN_FWD_PRIO_LO();
+    } else {
+      load_twin_feat(twins, src, h, feat);
+    }
+    MlpAct a;
+    f32x16 c2;
+    // skip_dead: a fine tile without density has no nonzero d raw, so the
+    // binned backward (dense_bwd = 0: its work lists) never reads its
+    // features or masks -- they are not stored.  (The coarse tiles' are: the twins.)
+    const bool dead_skip = pol.skip_dead(kPass);
+    bool stored = kPass == 0 || !dead_skip;
+    if (stored) pol.save_feat(kPass, tau, lane, feat);
+    mlp_fwd_tile_src<Pol::kMasks>(FragRing{P, ring}, feat, [&](int ob) { return c0sh_lds_load(L + kFC0, ob, lane); },
+                                  a, c2, lane, dead_skip, [&]() {
+                                    if (!stored) pol.save_feat(kPass, tau, lane, feat);
+                                    stored = true;
+                                  });
+    const float4 o4 = make_float4(c2[0], c2[1], c2[2], a.s1[0]);
+    if (stored) pol.save_masks(kPass, tau, lane, a.m);
+    if (h == 0) {
+      *reinterpret_cast<float4*>(L + kFRaw + 4 * q) = o4;
+      pol.save_raw(kPass, q, o4);
+    }
+  }
+}
+
+// render_fwd_kernel's policy: features and masks into the feature cache (where
+// there is one), whose coarse tiles are the twins; raw to global memory
+template <bool kLoss>
+struct TrainTiles {
+  static constexpr bool kMasks = true;
+  const RenderK& k;
+  int64_t ray;
+  const uint8_t* srcl;   // kLoss: the samples' origins in LDS
+  HN_DEV const float* twins() const { return k.feat ? k.feat + (size_t)ray * HN_RENDER_FEAT_PER_RAY : nullptr; }
+  // (kLoss: from the LDS copy -- no global round trip ahead of each tile's gathers)
+  HN_DEV int origin(int q) const { return kLoss ? (int)srcl[q] : (int)k.fine_src[ray * kSf + q]; }
+  HN_DEV bool skip_dead(int pass) const { return k.skip_dead && (pass ? k.noise_f : k.noise_c) == nullptr; }
+  HN_DEV void save_feat(int pass, int tau, int lane, const f32x16& feat) const {
+    if (k.feat) store_feat(k.feat, ray, pass * (kSc / 32) + tau, lane, feat, k.feat_nt != 0);
+  }
+  HN_DEV void save_masks(int pass, int tau, int lane, const uint32_t (&m)[3]) const {
+    if (k.feat) store_masks(k.feat, ray, pass * (kSc / 32) + tau, lane, m, k.feat_nt != 0);
+  }
+  HN_DEV void save_raw(int pass, int q, const float4& o4) const {
+    *reinterpret_cast<float4*>(pass ? k.raw_f + (ray * kSf + q) * 4 : k.raw_c + (ray * kSc + q) * 4) = o4;
+  }
+};
 
 // One pass's composite.  kLoss: then also the training loss's composite
 // backward from the same samples and totals (composite_bwd's two halves, so
@@ -44,7 +171,7 @@ template <bool kLoss, int N>
 HN_DEV void composite_pass(const RenderK& k, int64_t ray, float* rawb, const float* z, const float* noise, int S,
                            float dnorm, float* wout, CompOut& o, int lane) {
   if constexpr (!kLoss) {
-    composite_fwd<N>(rawb, z, noise, S, dnorm, k.white != 0, wout, o, lane);
+    composite_fwd<N>(rawb, z, noise, S, dnorm, k.f.white != 0, wout, o, lane);
   } else {
     // (the ray's target colour asked for ahead of the composite that hides its latency)
     const float target[3] = {k.ltarget[3 * ray], k.ltarget[3 * ray + 1], k.ltarget[3 * ray + 2]};
@@ -52,10 +179,10 @@ HN_DEV void composite_pass(const RenderK& k, int64_t ray, float* rawb, const flo
     composite_samples<N>(rawb, z, noise, S, dnorm, cs, lane);
     CompTotals t;
     composite_totals<N>(cs, t);
-    composite_fwd_out<N>(cs, t, k.white != 0, wout, o, lane);
+    composite_fwd_out<N>(cs, t, k.f.white != 0, wout, o, lane);
     CompGrad g;
     loss_comp_grad(g, k.lgm, k.lsparse, o.rgb[0], o.rgb[1], o.rgb[2], target);
-    composite_bwd_raw<N>(cs, t, k.white != 0, g, nullptr, nullptr, rawb, lane);
+    composite_bwd_raw<N>(cs, t, k.f.white != 0, g, nullptr, nullptr, rawb, lane);
     lds_fence_wave();
   }
 }
@@ -80,9 +207,8 @@ void render_fwd_kernel(RenderK k) {
   // 0.296 -> 0.281 ms (r04e)
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  const int p = lane & 31, h = lane >> 5;
   float* gsl = smem + kFwdBlockWaves * kFLds;
-  stage_grid_sizes(k.g, gsl);
+  stage_grid_sizes(k.f.g, gsl);
   __syncthreads();
   // XCD-aware: workgroup b runs on XCD b % 8, so consecutive ray groups of a
   // spatially ordered batch go to one XCD and share its L2
@@ -103,19 +229,12 @@ void render_fwd_kernel(RenderK k) {
   float* zs = L + kFZs;
   float* rawb = L + kFRaw;
   float* wts = L + kFW;
-  float* bins = L + kFBins;
-  float* cdf = L + kFCdf;
   Ray r;
   load_ray(k.rays, ray, r);
-  float sh8[8], shx8[8];
-  float* c0l = L + kFC0;
+  float sh8[8];
 
   // ---- coarse z_vals (:514-536) ----
-  auto zlin = [&](int i) {
-    const float t = k.tvals[i];
-    return k.lindisp ? 1.f / (1.f / r.near * (1.f - t) + 1.f / r.far * t)
-                     : r.near * (1.f - t) + r.far * t;
-  };
+  auto zlin = [&](int i) { return coarse_z(k.f.tvals[i], r.near, r.far, k.f.lindisp); };
   float z = zlin(lane);
   if (k.perturb) {
     const float zm = lane > 0 ? zlin(lane - 1) : z;
@@ -127,34 +246,16 @@ void render_fwd_kernel(RenderK k) {
   zc[lane] = z;
   zsrc[lane] = z;
   k.z_coarse[ray * kSc + lane] = z;
-  ray_sh(r, h, sh8, shx8);
+  ray_sh(r, lane >> 5, sh8);
   lds_fence_wave();
 
   // ---- coarse network (:540) ----
-  c0sh_lds_store(opaque_ptr(k.Pc), sh8, c0l, lane);
-  lds_fence_wave();
-  fwd_ring_start(k.Pc, fring[wave], lane);
-  for (int tau = 0; tau < kSc / 32; ++tau) {
-    const float* P = opaque_ptr(k.Pc);
-    const int q = 32 * tau + p;
-    float pt[3];
-    ray_point(r, zc[q], pt);
-    f32x16 feat;
-    HN_FWD_PRIO_HI();
-    encode_tile(k.g, gsl, k.table, pt, h, feat);
-    HN_FWD_PRIO_LO();
-    if (k.feat) store_feat(k.feat, ray, tau, lane, feat, k.feat_nt != 0);
-    MlpAct a;
-    f32x16 c2;
-    mlp_fwd_tile_src<true>(FragRing{P, fring[wave]}, feat, [&](int ob) { return c0sh_lds_load(c0l, ob, lane); },
-                           a, c2, lane, k.skip_dead && k.noise_c == nullptr);
-    if (k.feat) store_masks(k.feat, ray, tau, lane, a.m, k.feat_nt != 0);
-    if (h == 0) {
-      const float4 o4 = make_float4(c2[0], c2[1], c2[2], a.s1[0]);
-      *reinterpret_cast<float4*>(rawb + 4 * q) = o4;
-      *reinterpret_cast<float4*>(k.raw_c + (ray * kSc + q) * 4) = o4;
-    }
-  }
+  // kLoss: the samples' coarse origins kept in LDS for the marks (zsrc is free
+  // after the merge), read beside the first fine tile's own look at them
+  uint8_t* srcl = reinterpret_cast<uint8_t*>(zsrc);
+  TrainTiles<kLoss> pol{k, ray, srcl};
+  pass_start(k.f.Pc, sh8, L, fring[wave], lane, false);
+  pass_tiles<0>(k.f, gsl, fring[wave], L, r, lane, pol);
   lds_fence_wave();
   CompOut co;
   composite_pass<kLoss, kSc / 64>(k, ray, rawb, zc, k.noise_c ? k.noise_c + ray * kSc : nullptr, kSc, r.dnorm, wts,
@@ -176,86 +277,24 @@ void render_fwd_kernel(RenderK k) {
   }
 
   // ---- importance sampling (:547-551) ----
-  if (lane < kSc - 1) bins[lane] = .5f * (zc[lane + 1] + zc[lane]);
-  lds_fence_wave();
-  sample_pdf_wave(bins, wts + 1, kSc - 2, cdf, k.u + ray * kNi, kNi, zsrc + kSc, lane);
-  lds_fence_wave();
-  {
+  if (lane < kSc - 1) L[kFBins + lane] = .5f * (zc[lane + 1] + zc[lane]);
+  importance_sort(L, k.f.u + ray * kNi, k.fine_src + ray * kSf, lane);
+  {   // z_std of the samples as drawn (the sort reads zsrc only)
     const float s0 = zsrc[kSc + lane], s1 = zsrc[kSc + 64 + lane];
     const double mean = wave_sum((double)s0 + (double)s1) / kNi;
     const double d0 = (double)s0 - mean, d1 = (double)s1 - mean;
     const double var = wave_sum(d0 * d0 + d1 * d1) / kNi;
     if (lane == 0) k.z_std[ray] = (float)sqrt(var);
   }
-  // sort(cat(z_vals, z_samples)) (:551): a merge of the sorted coarse run with
-  // the bitonic-sorted importance samples (rawb is free until the fine tiles),
-  // the all-pairs rank sort if the coarse run is ever out of order
-  // (render_fwd_kernel 0.2998 -> 0.2966 ms, r04c)
-  uint8_t* org = k.fine_src + ray * kSf;
-  if (!merge_sort_z(zsrc, zs, rawb, lane, org)) rank_sort_wave(zsrc, zs, kSf, lane, org, kSc);
   for (int i = lane; i < kSf; i += 64) k.z_fine[ray * kSf + i] = zs[i];
 
   // ---- fine network (:556) ----
-  c0sh_lds_store(opaque_ptr(k.Pf), sh8, c0l, lane);   // the coarse tiles' reads are done (in-order LDS)
-  lds_fence_wave();
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the coarse ring's last (unused) fill has landed
-  fwd_ring_start(k.Pf, fring[wave], lane);
-  // kLoss: the samples' coarse origins kept in LDS for the marks (zsrc is free
-  // after the merge), read beside the first fine tile's own look at them
-  uint8_t* srcl = reinterpret_cast<uint8_t*>(zsrc);
+  pass_start(k.f.Pf, sh8, L, fring[wave], lane, true);
   if constexpr (kLoss) {
     for (int i = lane; i < kSf; i += 64) srcl[i] = k.fine_src[ray * kSf + i];
     lds_fence_wave();
   }
-  for (int tau = 0; tau < kSf / 32; ++tau) {
-    const float* P = opaque_ptr(k.Pf);
-    const int q = 32 * tau + p;
-    float pt[3];
-    ray_point(r, zs[q], pt);
-    f32x16 feat;
-    // a third of the fine samples are the coarse samples again (the merge
-    // keeps their z bitwise): with the feature cache present, those lanes load
-    // the coarse tile's features (4 dwordx4, written by this wave) instead of
-    // gathering 16 levels x 8 corners again -- a quarter of the ray's gathers
-    // (render_fwd_kernel 0.282 -> 0.275 ms, r04h).  Encoding only the 128
-    // importance samples as 4 full tiles first and loading every fine tile's
-    // features back from the cache (a third fewer encode instructions) measured
-    // slower: 0.301 ms, the waves then run their MLP tiles in step (r04j).
-    // (kLoss: from the LDS copy -- no global round trip ahead of each tile's gathers)
-    const int src = !k.feat ? 255 : kLoss ? (int)srcl[q] : (int)k.fine_src[ray * kSf + q];
-    if (src >= kSc) {
-      HN_FWD_PRIO_HI();
-      encode_tile(k.g, gsl, k.table, pt, h, feat);
-      HN_FWD_PRIO_LO();
-    } else {
-      const f32x4* t = reinterpret_cast<const f32x4*>(k.feat + (size_t)ray * HN_RENDER_FEAT_PER_RAY +
-                                                      (size_t)(src >> 5) * 1024) + (src & 31) + 32 * h;
-#pragma unroll
-      for (int c = 0; c < 4; ++c) {
-        const f32x4 v = t[64 * c];
-        feat[4 * c] = v.x; feat[4 * c + 1] = v.y; feat[4 * c + 2] = v.z; feat[4 * c + 3] = v.w;
-      }
-    }
-    MlpAct a;
-    f32x16 c2;
-    // skip_dead: a fine tile without density has no nonzero d raw, so the
-    // binned backward (dense_bwd = 0: its work lists) never reads its
-    // features or masks -- they are not stored
-    const bool dead_skip = k.skip_dead && k.noise_f == nullptr;
-    bool stored = !dead_skip;
-    if (k.feat && stored) store_feat(k.feat, ray, kSc / 32 + tau, lane, feat, k.feat_nt != 0);
-    mlp_fwd_tile_src<true>(FragRing{P, fring[wave]}, feat, [&](int ob) { return c0sh_lds_load(c0l, ob, lane); },
-                           a, c2, lane, dead_skip, [&]() {
-                             if (k.feat && !stored) store_feat(k.feat, ray, kSc / 32 + tau, lane, feat, k.feat_nt != 0);
-                             stored = true;
-                           });
-    if (k.feat && stored) store_masks(k.feat, ray, kSc / 32 + tau, lane, a.m, k.feat_nt != 0);
-    if (h == 0) {
-      const float4 o4 = make_float4(c2[0], c2[1], c2[2], a.s1[0]);
-      *reinterpret_cast<float4*>(rawb + 4 * q) = o4;
-      *reinterpret_cast<float4*>(k.raw_f + (ray * kSf + q) * 4) = o4;
-    }
-  }
+  pass_tiles<1>(k.f, gsl, fring[wave], L, r, lane, pol);
   lds_fence_wave();
   CompOut fo;
   composite_pass<kLoss, kSf / 64>(k, ray, rawb, zs, k.noise_f ? k.noise_f + ray * kSf : nullptr, kSf, r.dnorm,

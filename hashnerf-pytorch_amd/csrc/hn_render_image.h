@@ -8,6 +8,12 @@
 // backward: z, raw and the samples' coarse origins live in LDS, the two coarse
 // feature tiles a fine pass takes its coarse twins from in a slot of the
 // workspace that the wave owns for the whole launch.
+//
+// The passes are hn_render_fwd.h's shared body (coarse_z, pass_start,
+// pass_tiles, importance_sort); this file holds the kernel's arguments, the
+// pixel mapping, the persistent loop and ImageTiles, the policy for a tile's
+// results: no masks, no stores but the coarse tiles into the slot, every dead
+// tile's colours skipped.
 #pragma once
 #include "hn_render_fwd.h"
 #include "hn_sampler.h"
@@ -26,18 +32,13 @@ constexpr int kImgTile = 8;
 enum : int { kImgReencode = 1, kImgRowMajor = 2 };
 
 struct ImageK {
-  GridArgs g;
-  int white, lindisp, variant;
+  FieldK f;
+  int variant;
   int n_views, H, W, pose_stride;
   uint32_t Hb, Wb;       // the image in 2 x 2 pixel blocks
   uint32_t groups;       // ray groups (4 rays) of the launch
   float fx, fy, cx, cy, near, far;
   const float* poses;
-  const float* tvals;
-  const float* u;
-  const float* table;
-  const float* Pc;
-  const float* Pf;
   float* slots;          // [4 kImgBlocks][kImgSlotFloats], or NULL: every fine sample encoded
   float *rgb, *depth, *acc, *rays;
 };
@@ -88,6 +89,21 @@ HN_DEV void image_group_block(uint32_t Hb, uint32_t Wb, uint32_t grp, uint32_t& 
   by = ty * kImgTile + dy;
 }
 
+// render_image_kernel's policy for the shared tile loops (hn_render_fwd.h)
+struct ImageTiles {
+  static constexpr bool kMasks = false;
+  float* slot;           // the wave's two coarse tiles, or NULL: every fine sample encoded
+  const uint8_t* srcl;   // the fine samples' coarse origins (LDS)
+  HN_DEV const float* twins() const { return slot; }
+  HN_DEV int origin(int q) const { return (int)srcl[q]; }
+  HN_DEV bool skip_dead(int) const { return true; }
+  HN_DEV void save_feat(int pass, int tau, int lane, const f32x16& feat) const {
+    if (pass == 0 && slot) store_feat(slot, 0, tau, lane, feat, false);
+  }
+  HN_DEV void save_masks(int, int, int, const uint32_t (&)[3]) const {}
+  HN_DEV void save_raw(int, int, const float4&) const {}
+};
+
 HN_DEV float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
 __global__ __launch_bounds__(64 * kFwdBlockWaves)
@@ -99,7 +115,7 @@ void render_image_kernel(ImageK k) {
   const int lane0 = threadIdx.x & 63;
   float* gsl = smem + kFwdBlockWaves * kFLds;
   const float* pixl = gsl + kGsLds;
-  stage_grid_sizes(k.g, gsl);
+  stage_grid_sizes(k.f.g, gsl);
   if (threadIdx.x == 64) {
     ImagePix x;
     x.fx = k.fx; x.fy = k.fy; x.cx = k.cx; x.cy = k.cy; x.near = k.near; x.far = k.far;
@@ -118,15 +134,12 @@ void render_image_kernel(ImageK k) {
   // are the launch's, so every ray of the wave shares them ----
   {
     const int lane = lane0;
-    float* zc = smem + wave * kFLds + kFZc;
-    float* zsrc = smem + wave * kFLds + kFZsrc;
-    float* bins = smem + wave * kFLds + kFBins;
-    const float t = k.tvals[lane];
-    const float z = k.lindisp ? 1.f / (1.f / k.near * (1.f - t) + 1.f / k.far * t) : k.near * (1.f - t) + k.far * t;
-    zc[lane] = z;
-    zsrc[lane] = z;
+    float* L = smem + wave * kFLds;
+    const float z = coarse_z(k.f.tvals[lane], k.near, k.far, k.f.lindisp);
+    L[kFZc + lane] = z;
+    L[kFZsrc + lane] = z;
     lds_fence_wave();
-    if (lane < kSc - 1) bins[lane] = .5f * (zc[lane + 1] + zc[lane]);
+    if (lane < kSc - 1) L[kFBins + lane] = .5f * (L[kFZc + lane + 1] + L[kFZc + lane]);
     lds_fence_wave();
   }
 
@@ -146,19 +159,10 @@ void render_image_kernel(ImageK k) {
     // scalar registers through it (87 scalar spills)
     int lane = lane0, woff = wave * kFLds;
     asm volatile("" : "+v"(lane), "+s"(woff));
-    const int p = lane & 31, h = lane >> 5;
     float* L = smem + woff;
-    float* zc = L + kFZc;
-    float* zsrc = L + kFZsrc;
-    float* zs = L + kFZs;
-    float* rawb = L + kFRaw;
-    float* wts = L + kFW;
-    float* bins = L + kFBins;
-    float* cdf = L + kFCdf;
-    float* c0l = L + kFC0;
     // the fine samples' coarse origins: over the coarse weights, which
     // sample_pdf_wave has consumed by the time the merge writes them
-    uint8_t* srcl = reinterpret_cast<uint8_t*>(wts);
+    uint8_t* srcl = reinterpret_cast<uint8_t*>(L + kFW);
     // ---- the wave's pixel and its ray ----
     int64_t ray;
     Ray r;
@@ -191,85 +195,30 @@ void render_image_kernel(ImageK k) {
       }
       // the ray on the scalar unit, as the forward's loaded one
 #pragma unroll
-      for (int a = 0; a < 3; ++a) {
-        r.o[a] = wave_uniform(v[a]);
-        r.d[a] = wave_uniform(v[3 + a]);
-        r.vd[a] = wave_uniform(v[8 + a]);
-      }
-      r.near = x.near;
-      r.far = x.far;
-      r.dnorm = wave_uniform(sqrtf(r.d[0] * r.d[0] + r.d[1] * r.d[1] + r.d[2] * r.d[2]));   // load_ray's
+      for (int a = 0; a < 11; ++a) v[a] = wave_uniform(v[a]);
+      make_ray(v, r);
+      r.dnorm = wave_uniform(r.dnorm);
     }
-    float sh8[8], shx8[8];
-    ray_sh(r, h, sh8, shx8);
+    float sh8[8];
+    ray_sh(r, lane >> 5, sh8);
+    ImageTiles pol{slot, srcl};
 
-    // ---- coarse network (:540) ----
-    c0sh_lds_store(opaque_ptr(k.Pc), sh8, c0l, lane);   // the last ray's tiles have read theirs (in-order LDS)
-    lds_fence_wave();
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the last ray's final (unused) ring fill has landed
-    fwd_ring_start(k.Pc, fring[wave], lane);
-    for (int tau = 0; tau < kSc / 32; ++tau) {
-      const float* P = opaque_ptr(k.Pc);
-      const int q = 32 * tau + p;
-      float pt[3];
-      ray_point(r, zc[q], pt);
-      f32x16 feat;
-      HN_FWD_PRIO_HI();
-      encode_tile(k.g, gsl, k.table, pt, h, feat);
-      HN_FWD_PRIO_LO();
-      if (slot) store_feat(slot, 0, tau, lane, feat, false);
-      MlpAct a;
-      f32x16 c2;
-      mlp_fwd_tile_src<false>(FragRing{P, fring[wave]}, feat, [&](int ob) { return c0sh_lds_load(c0l, ob, lane); },
-                              a, c2, lane, true);
-      if (h == 0) *reinterpret_cast<float4*>(rawb + 4 * q) = make_float4(c2[0], c2[1], c2[2], a.s1[0]);
-    }
+    // ---- coarse network (:540); the last ray's final (unused) ring fill drained ----
+    pass_start(k.f.Pc, sh8, L, fring[wave], lane, true);
+    pass_tiles<0>(k.f, gsl, fring[wave], L, r, lane, pol);
     lds_fence_wave();
     CompOut co;
-    composite_fwd<kSc / 64>(rawb, zc, nullptr, kSc, r.dnorm, k.white != 0, wts, co, lane);
+    composite_fwd<kSc / 64>(L + kFRaw, L + kFZc, nullptr, kSc, r.dnorm, k.f.white != 0, L + kFW, co, lane);
 
     // ---- importance sampling (:547-551), the det uniforms ----
-    lds_fence_wave();
-    sample_pdf_wave(bins, wts + 1, kSc - 2, cdf, k.u, kNi, zsrc + kSc, lane);
-    lds_fence_wave();
-    if (!merge_sort_z(zsrc, zs, rawb, lane, srcl)) rank_sort_wave(zsrc, zs, kSf, lane, srcl, kSc);
+    importance_sort(L, k.f.u, srcl, lane);
 
-    // ---- fine network (:556) ----
-    c0sh_lds_store(opaque_ptr(k.Pf), sh8, c0l, lane);
-    lds_fence_wave();
-    // the coarse ring's last (unused) fill has landed, and the slot's tiles are written
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    fwd_ring_start(k.Pf, fring[wave], lane);
-    for (int tau = 0; tau < kSf / 32; ++tau) {
-      const float* P = opaque_ptr(k.Pf);
-      const int q = 32 * tau + p;
-      float pt[3];
-      ray_point(r, zs[q], pt);
-      f32x16 feat;
-      // a coarse sample again (the merge keeps its z bitwise): its features
-      // from the wave's slot, as the training forward takes them from its cache
-      const int src = slot ? (int)srcl[q] : 255;
-      if (src >= kSc) {
-        HN_FWD_PRIO_HI();
-        encode_tile(k.g, gsl, k.table, pt, h, feat);
-        HN_FWD_PRIO_LO();
-      } else {
-        const f32x4* t = reinterpret_cast<const f32x4*>(slot + (size_t)(src >> 5) * 1024) + (src & 31) + 32 * h;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const f32x4 v = t[64 * c];
-          feat[4 * c] = v.x; feat[4 * c + 1] = v.y; feat[4 * c + 2] = v.z; feat[4 * c + 3] = v.w;
-        }
-      }
-      MlpAct a;
-      f32x16 c2;
-      mlp_fwd_tile_src<false>(FragRing{P, fring[wave]}, feat, [&](int ob) { return c0sh_lds_load(c0l, ob, lane); },
-                              a, c2, lane, true);
-      if (h == 0) *reinterpret_cast<float4*>(rawb + 4 * q) = make_float4(c2[0], c2[1], c2[2], a.s1[0]);
-    }
+    // ---- fine network (:556); the drain: the slot's tiles are written ----
+    pass_start(k.f.Pf, sh8, L, fring[wave], lane, true);
+    pass_tiles<1>(k.f, gsl, fring[wave], L, r, lane, pol);
     lds_fence_wave();
     CompOut fo;
-    composite_fwd<kSf / 64>(rawb, zs, nullptr, kSf, r.dnorm, k.white != 0, nullptr, fo, lane);
+    composite_fwd<kSf / 64>(L + kFRaw, L + kFZs, nullptr, kSf, r.dnorm, k.f.white != 0, nullptr, fo, lane);
     if (lane == 0) {
       ImagePix x;
       image_pix_load(pixl, x);

@@ -75,6 +75,20 @@ def _ws(nbytes: int, device) -> torch.Tensor:
     return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=device)
 
 
+def _ws_size(wsb) -> int:
+    return wsb.numel() * wsb.element_size()
+
+
+def _caller_ws(who: str, wsb, nbytes: int, dev):
+    """A call's workspace and its size in bytes: the caller's wsb (contiguous,
+    on dev, >= nbytes), or without one a fresh buffer of nbytes."""
+    if wsb is None:
+        return _ws(nbytes, dev), nbytes
+    if _ws_size(wsb) < nbytes or not wsb.is_contiguous() or wsb.device != dev:
+        raise ValueError(f"hashnerf_amd.{who}: wsb must be a contiguous buffer of >= {nbytes} bytes on {dev}")
+    return wsb, _ws_size(wsb)
+
+
 def _no_input_grad(name, *ts):
     for t in ts:
         if t is not None and t.requires_grad and torch.is_grad_enabled():
@@ -272,13 +286,7 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     feat = torch.empty((B, L.RENDER_FEAT_PER_RAY) if keep_feat else (0,), dtype=torch.float32,
                        device=dev)
     a.feat = feat.data_ptr() if keep_feat else None
-    nbytes = L.lib().hn_render_workspace_bytes(cfg, B)
-    if wsb is None:
-        wsb = _ws(nbytes, dev)
-    elif wsb.numel() * wsb.element_size() < nbytes or not wsb.is_contiguous() or wsb.device != dev:
-        raise ValueError(f"hashnerf_amd.render_fwd: wsb must be a contiguous buffer of >= {nbytes} bytes on {dev}")
-    else:
-        nbytes = wsb.numel() * wsb.element_size()
+    wsb, nbytes = _caller_ws("render_fwd", wsb, L.lib().hn_render_workspace_bytes(cfg, B), dev)
     a.weights_packed = 1 if weights_packed else 0
     a.skip_dead_color = 1 if skip_dead_color else 0
     la = None
@@ -889,7 +897,7 @@ def tv_bwd_records(cfg, table, mv, cubes, g_tv, d_table, wsb=None):
     if not d_table.is_contiguous() or d_table.shape != table.shape:
         raise ValueError("hashnerf_amd.tv_bwd_records: d_table must be a contiguous tensor shaped like the table")
     nbytes = L.lib().hn_render_workspace_bytes(cfg, 0)
-    if wsb is None or wsb.numel() * wsb.element_size() < nbytes:
+    if wsb is None or _ws_size(wsb) < nbytes:   # (a workspace too small is replaced, not refused)
         wsb = _ws(nbytes, table.device)
     a = L.HnRenderBwdArgs()
     a.n_rays = 0
@@ -899,8 +907,7 @@ def tv_bwd_records(cfg, table, mv, cubes, g_tv, d_table, wsb=None):
     a.g_tv = g.data_ptr()
     a.d_table = d_table.data_ptr()
     a.d_table_mode = 1
-    L.check(L.lib().hn_render_bwd(cfg, a, L.ptr(wsb), wsb.numel() * wsb.element_size(), L.stream(table.device)),
-            "render_bwd (TV only)")
+    L.check(L.lib().hn_render_bwd(cfg, a, L.ptr(wsb), _ws_size(wsb), L.stream(table.device)), "render_bwd (TV only)")
     if CHECK_FAULTS:
         L.check_device_faults()
     return wsb
@@ -1019,13 +1026,7 @@ def render_image(cfg, H, W, K, poses, near, far, table, ws, t_vals=None, u=None,
     a.coarse = L.make_mlp(ws[:5])
     a.fine = L.make_mlp(ws[5:])
     a.weights_packed = 1 if weights_packed else 0
-    nbytes = L.lib().hn_render_image_workspace_bytes(cfg)
-    if wsb is None:
-        wsb = _ws(nbytes, dev)
-    elif wsb.numel() * wsb.element_size() < nbytes or not wsb.is_contiguous() or wsb.device != dev:
-        raise ValueError(f"hashnerf_amd.render_image: wsb must be a contiguous buffer of >= {nbytes} bytes on {dev}")
-    else:
-        nbytes = wsb.numel() * wsb.element_size()
+    wsb, nbytes = _caller_ws("render_image", wsb, L.lib().hn_render_image_workspace_bytes(cfg), dev)
     t0 = TIMER.begin("render_image")
     if variant:
         L.check(L.lib().hn_render_image_variant(cfg, a, int(variant), L.ptr(wsb), nbytes, L.stream(dev)),

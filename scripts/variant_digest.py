@@ -1,7 +1,9 @@
 """Digest of one fused forward + backward at the bench shape (4096 rays,
 T=19, seeded inputs) with the library HN_LIB_PATH selects: sha256 of the
-table gradient, the ten MLP gradients and the forward state, so that variant
-libraries that must be bitwise equal can be compared across processes.
+table gradient, the ten MLP gradients and the forward state, and of
+hn_render_image's outputs on the image test's scene (3 views of 37 x 43, T =
+14), so that variant libraries that must be bitwise equal can be compared
+across processes.
   usage: HN_LIB_PATH=... python scripts/variant_digest.py [B] [T] [finest]"""
 import hashlib
 import os
@@ -15,6 +17,7 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 import hn_loader  # noqa: E402
 
 hn = hn_loader.load()
+from test_gpu_render_image import Scene  # noqa: E402
 from test_gpu_scatter import _bwd, _state  # noqa: E402
 
 B = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
@@ -28,3 +31,4 @@ f1 = h(st.z_f, st.raw_c, st.raw_f, st.feat)
 print(f"fwd {f0} table {h(tab)} mlp {h(*dws)}" + ("" if f1 == f0 else f" CHANGED-BY-BWD {f1}"))
 if os.environ.get("HN_DIGEST_PARTS"):
     print("  parts z_f %s raw_c %s raw_f %s feat %s" % (h(st.z_f), h(st.raw_c), h(st.raw_f), h(st.feat)))
+print("image " + h(*Scene(hn).image(HF, return_rays=True)))   # rgb, depth, acc, rays
