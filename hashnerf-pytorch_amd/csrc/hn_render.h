@@ -429,4 +429,50 @@ HN_DEV bool merge_sort_z(const float* src, float* dst, float* tmp, int lane, uin
   return true;
 }
 
+// merge_sort_z for src = [64 coarse z, non-decreasing | 64 importance z]: the
+// same result as rank_sort_wave(src, dst, 128, lane, origin, 64).  One
+// importance sample per lane, so the bitonic network (6 stages, 21 exchanges)
+// never leaves the wave's one register; then the same two binary searches
+// (coarse before importance on ties).  tmp: 64 floats.
+HN_DEV bool merge_sort_z64(const float* src, float* dst, float* tmp, int lane, uint8_t* origin) {
+  const float zc = src[lane];
+  const float zn = lane < 63 ? src[lane + 1] : zc;
+  if (__ballot(sort_key(zn) < sort_key(zc)) != 0ull) return false;
+  uint32_t k = sort_key(src[64 + lane]);
+#pragma unroll
+  for (int kk = 2; kk <= 64; kk <<= 1) {
+#pragma unroll
+    for (int j = kk >> 1; j > 0; j >>= 1) {
+      const uint32_t kp = shfl_from(k, lane ^ j);
+      const bool asc = (lane & kk) == 0, lower = (lane & j) == 0;   // kk = 64: ascending over the wave
+      k = (lower == asc) ? min(k, kp) : max(k, kp);
+    }
+  }
+  tmp[lane] = key_value(k);
+  lds_fence_wave();
+  // coarse e: e + #{importance < v} (lower bound in the sorted importance run)
+  {
+    const uint32_t kc = sort_key(zc);
+    int lo = 0, hi = 64;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sort_key(tmp[mid]) < kc) lo = mid + 1; else hi = mid;
+    }
+    dst[lane + lo] = zc;
+    if (origin) origin[lane + lo] = (uint8_t)lane;
+  }
+  // importance at sorted position lane: lane + #{coarse <= v} (upper bound in the coarse run)
+  {
+    int lo = 0, hi = 64;
+    while (lo < hi) {
+      const int mid = (lo + hi) >> 1;
+      if (sort_key(src[mid]) <= k) lo = mid + 1; else hi = mid;
+    }
+    dst[lane + lo] = key_value(k);
+    if (origin) origin[lane + lo] = (uint8_t)255;
+  }
+  lds_fence_wave();
+  return true;
+}
+
 }  // namespace hn

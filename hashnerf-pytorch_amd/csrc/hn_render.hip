@@ -45,7 +45,7 @@ __global__ __launch_bounds__(256) void render_comp_bwd_kernel(B1K k) {
   const bool fine = (w & 1) != 0;
   float* rawb = lds[wave] + kSf;
   if (active) {
-    const int S = fine ? kSf : kSc;
+    const int S = fine ? k.sf : kSc;   // (the d raw below keep the 64 + 192 stride)
     float* zb = lds[wave];
     const float* zsrc = (fine ? k.z_fine : k.z_coarse) + ray * S;
     const float* rsrc = (fine ? k.raw_f : k.raw_c) + ray * S * 4;
@@ -79,8 +79,10 @@ __global__ __launch_bounds__(256) void render_comp_bwd_kernel(B1K k) {
                               : (k.noise_c ? k.noise_c + ray * S : nullptr);
     const float* graw = (fine && k.g_raw_f) ? k.g_raw_f + ray * S * 4 : nullptr;
     float* dst = k.draw + ((size_t)ray * (kSc + kSf) + (fine ? kSc : 0)) * 4;
-    if (fine)
+    if (fine && S == kSf)
       composite_bwd<kSf / 64>(rawb, zb, noise, S, r.dnorm, k.white != 0, g, nullptr, graw, rawb, lane);
+    else if (fine)
+      composite_bwd<kSf64 / 64>(rawb, zb, noise, S, r.dnorm, k.white != 0, g, nullptr, graw, rawb, lane);
     else
       composite_bwd<kSc / 64>(rawb, zb, noise, S, r.dnorm, k.white != 0, g, nullptr, graw, rawb, lane);
     lds_fence_wave();
@@ -93,7 +95,9 @@ __global__ __launch_bounds__(256) void render_comp_bwd_kernel(B1K k) {
   __syncthreads();
   if (active && fine) {
     // the scatter's marks (bits 20-31), beside the fine MLP groups (8-19)
-    const uint32_t su = scatter_marks(rawb, k.fine_src + ray * kSf, cmask[wave >> 1], lane);
+    const uint8_t* src = k.fine_src + ray * k.sf;
+    const uint32_t su = k.sf == kSf ? scatter_marks<kSf>(rawb, src, cmask[wave >> 1], lane)
+                                    : scatter_marks<kSf64>(rawb, src, cmask[wave >> 1], lane);
     if (lane == 0) store_fine_marks(k.uflags, ray, nzf, su);
   }
 }
@@ -105,11 +109,16 @@ static int32_t check_cfg(const hn_render_cfg* c) {
   const hn_grid& g = c->grid;
   if (g.n_levels != 16 || g.n_features != 2) return HN_E_SHAPE;
   if (g.log2_hashmap_size < 1 || g.log2_hashmap_size > 24) return HN_E_SHAPE;
-  if (c->n_samples != kSc || c->n_importance != kNi) return HN_E_SHAPE;
+  if (c->n_samples != kSc || (c->n_importance != kNi && c->n_importance != kNi64)) return HN_E_SHAPE;
   if (c->scatter < 0 || c->scatter > 2) return HN_E_SHAPE;
   if (c->bin_cap < 0 || (c->bin_cap & 63)) return HN_E_SHAPE;
   if (c->dense_bwd < 0 || c->dense_bwd > 1) return HN_E_SHAPE;
   return HN_OK;
+}
+// The whole-image kernel renders 64 + 128 samples only
+static int32_t check_image_cfg(const hn_render_cfg* c) {
+  const int32_t st = check_cfg(c);
+  return st ? st : (c->n_importance != kNi ? HN_E_SHAPE : HN_OK);
 }
 
 static bool mlp_ok(const hn_mlp& w) { return w.sigma0 && w.sigma1 && w.color0 && w.color1 && w.color2; }
@@ -352,6 +361,10 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
   if (!workspace) return HN_E_NULL;
   const BwdPlan plan = bwd_plan(cfg, a->n_rays);
   if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
+  // 64 importance samples: only the binned backward reads such a forward's
+  // state, so a training forward (feat) on the float-atomic schedule is refused
+  const bool ni64 = cfg->n_importance == kNi64;
+  if (ni64 && a->feat && plan.mode != kModeSplit) return HN_E_SHAPE;
   if (a->loss) {   // the composite backward of the training loss done here (only target, world, sparse_w read)
     if (!a->loss->target) return HN_E_NULL;
     if (!(a->loss->world > 0.f)) return HN_E_SHAPE;
@@ -390,9 +403,14 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
     k.draw = w.draw;
     k.uflags = w.uflags;
     k.stamp = ws_stamp(w.lmeta);
-    hipLaunchKernelGGL(render_fwd_kernel<true>, dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+    if (ni64)
+      hipLaunchKernelGGL((render_fwd_kernel<true, kNi64>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+    else
+      hipLaunchKernelGGL((render_fwd_kernel<true, kNi>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+  } else if (ni64) {
+    hipLaunchKernelGGL((render_fwd_kernel<false, kNi64>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
   } else {
-    hipLaunchKernelGGL(render_fwd_kernel<false>, dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+    hipLaunchKernelGGL((render_fwd_kernel<false, kNi>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
   }
   return hip_status(hipGetLastError());
 }
@@ -402,12 +420,12 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
 static size_t image_ws_floats() { return (size_t)2 * G_END + (size_t)kImgBlocks * kFwdBlockWaves * kImgSlotFloats; }
 
 extern "C" size_t hn_render_image_workspace_bytes(const hn_render_cfg* cfg) {
-  return check_cfg(cfg) ? 0 : image_ws_floats() * sizeof(float);
+  return check_image_cfg(cfg) ? 0 : image_ws_floats() * sizeof(float);
 }
 
 extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
                                            void* workspace, size_t ws_bytes, void* stream) {
-  int32_t st = check_cfg(cfg);
+  int32_t st = check_image_cfg(cfg);
   if (st) return st;
   if (!a) return HN_E_NULL;
   if (cfg->perturb) return HN_E_SHAPE;   // the stratified jitter is the training forward's
@@ -569,7 +587,10 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
   sk.overwrite_mlp = (a->d_table_mode & 2) ? 1 : 0;
   sk.has_mstep = a->mlp_step != nullptr;
   for (int t = 0; t < 10; ++t) sk.mstep[t] = sk.has_mstep ? a->mlp_step[t] : hn_radam_tensor{};
-  hipLaunchKernelGGL(scatter_bins_kernel, dim3(kBwdBlocks), dim3(64 * kScWaves), plan.sc_lds, s, sk);
+  if (k.sf == kSf)
+    hipLaunchKernelGGL(scatter_bins_kernel, dim3(kBwdBlocks), dim3(64 * kScWaves), plan.sc_lds, s, sk);
+  else
+    hipLaunchKernelGGL(scatter_bins_kernel64, dim3(kBwdBlocks), dim3(64 * kScWaves), plan.sc_lds, s, sk);
   if ((st = hip_status(hipGetLastError()))) return st;
   const BinR r = owner_args(cfg, a, k.bins, plan.bg, 0);
   PackK pk{};
@@ -638,6 +659,7 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   const BwdPlan plan = bwd_plan(cfg, a->n_rays);
   const bool binned = plan.mode == kModeSplit;
   if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
+  if (cfg->n_importance == kNi64 && !binned) return HN_E_SHAPE;   // the float-atomic schedule is 64 + 128 only
   // the next batch's job: hn_sample_batch_morton's checks and codes, before anything is queued
   NextK nk{};
   if (a->next_batch) {
@@ -726,6 +748,7 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   k.lgm = k.lsparse = k.lworld = k.lsparse_w = k.ltv_w = 0.f;
   k.lout = nullptr;
   k.skip_zero = cfg->dense_bwd ? 0 : 1;
+  k.sf = kSc + cfg->n_importance;
   if (a->loss) {
     const hn_render_loss& L = *a->loss;
     const float g = 1.f;   // hn_loss_bwd's factors with g_loss = 1

@@ -18,6 +18,12 @@ namespace hn {
 constexpr int kEncGroup = 2;
 
 constexpr int kSc = 64, kNi = 128, kSf = 192;
+// The second fine-pass shape (hn_render_cfg.n_importance = 64, the LLFF
+// configurations): 128 fine samples = 4 tiles = 8 groups of 16.  The caller's
+// per-ray tensors take its strides; the workspace (d raw, marks, lists, fine
+// feature grads) and the feature cache keep the 64 + 128 strides, their tails
+// unused.
+constexpr int kNi64 = 64, kSf64 = kSc + kNi64;
 constexpr int kFwdWaves = 4;
 constexpr int kBwdBlocks = 256;          // persistent backward: one block per CU
 
@@ -86,10 +92,12 @@ struct B1K {
   float lgm, lsparse, lworld, lsparse_w, ltv_w;
   float* lout;
   int32_t skip_zero;    // exact-zero skipping (!hn_render_cfg.dense_bwd)
+  int32_t sf;           // fine samples per ray (kSf or kSf64): the stride of z_fine, raw_f, noise_f,
+                        // g_raw_f, fine_src (the pre-pass, the lists' dense word)
   uint8_t* uflags;      // [B][kMarkB] marks (composite pre-pass): [0] coarse, [1] fine MLP tiles with a
                         // nonzero d raw -- as bits: 0-3 coarse 16-sample groups, 8-19 fine
                         // groups (the MLP backward's), 20-31 fine groups with a nonzero sample or
-                        // coarse twin (the scatter's)
+                        // coarse twin (the scatter's); sf = kSf64: 8 fine groups, bits 8-15 and 20-27
   int32_t* lmeta;       // work lists (render_lists_kernel): [0] coarse tiles, [1] fine tiles, [2] scatter
                         // tiles, [3] gsplit: the MLP waves g < gsplit run coarse tiles (slab_reduce_block)
   int32_t* lists;       // group codes (ray << 4 | group): coarse [4B] | fine [12B] | the scatter's [12B]
@@ -335,11 +343,12 @@ HN_DEV unsigned long long coarse_nonzero_mask(const float* rawb, int lane) {
 }
 // The scatter's marks of a ray: bit t = a sample of fine group t, or its
 // coarse twin (the same point, fine_src < 64; cm = coarse_nonzero_mask), has a
-// nonzero d raw -- the group has feature grads to scatter.
+// nonzero d raw -- the group has feature grads to scatter.  kS: the ray's fine samples.
+template <int kS = kSf>
 HN_DEV uint32_t scatter_marks(const float* rawb, const uint8_t* __restrict__ fine_src, unsigned long long cm,
                               int lane) {
   uint32_t su = 0u;
-  for (int j = lane; j < kSf; j += 64) {
+  for (int j = lane; j < kS; j += 64) {
     const int src = fine_src[j];
     const bool nz = draw_nonzero(*reinterpret_cast<const float4*>(rawb + 4 * j)) ||
                     (src < kSc && ((cm >> src) & 1ull) != 0ull);
@@ -348,7 +357,8 @@ HN_DEV uint32_t scatter_marks(const float* rawb, const uint8_t* __restrict__ fin
   return su;
 }
 // Mark bytes 1-3 of a ray (bits 8-19: the fine MLP groups nzf, 20-31: the
-// scatter's groups su); byte 0 is the coarse pass's MLP groups.
+// scatter's groups su); byte 0 is the coarse pass's MLP groups.  A 128-sample
+// fine pass has 8 groups: bits 8-15 and 20-27, the others stay 0.
 HN_DEV void store_fine_marks(uint8_t* __restrict__ uflags, int64_t ray, uint32_t nzf, uint32_t su) {
   const uint32_t v = nzf | (su << 12);
   uflags[kMarkB * ray + 1] = (uint8_t)v;

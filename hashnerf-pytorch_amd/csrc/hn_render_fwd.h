@@ -83,21 +83,39 @@ HN_DEV void load_twin_feat(const float* tiles, int src, int h, f32x16& feat) {
 // (rawb is free until the fine tiles), the all-pairs rank sort if the coarse
 // run is ever out of order (render_fwd_kernel 0.2998 -> 0.2966 ms, r04c).
 // zsrc keeps the samples as drawn; org[i]: sorted sample i's coarse origin.
+// kNiT: the importance samples, kNi or kNi64 (its own one-register merge).
+template <int kNiT = kNi>
 HN_DEV void importance_sort(float* L, const float* u, uint8_t* org, int lane) {
+  static_assert(kNiT == kNi || kNiT == kNi64, "importance_sort: 128 or 64 importance samples");
   float* zsrc = L + kFZsrc;
   lds_fence_wave();
-  sample_pdf_wave(L + kFBins, L + kFW + 1, kSc - 2, L + kFCdf, u, kNi, zsrc + kSc, lane);
+  sample_pdf_wave(L + kFBins, L + kFW + 1, kSc - 2, L + kFCdf, u, kNiT, zsrc + kSc, lane);
   lds_fence_wave();
-  if (!merge_sort_z(zsrc, L + kFZs, L + kFRaw, lane, org)) rank_sort_wave(zsrc, L + kFZs, kSf, lane, org, kSc);
+  if constexpr (kNiT == kNi) {
+    if (!merge_sort_z(zsrc, L + kFZs, L + kFRaw, lane, org)) rank_sort_wave(zsrc, L + kFZs, kSf, lane, org, kSc);
+  } else {
+    if (!merge_sort_z64(zsrc, L + kFZs, L + kFRaw, lane, org))
+      rank_sort_wave(zsrc, L + kFZs, kSc + kNiT, lane, org, kSc);
+  }
 }
 
 // A pass's tiles: kPass 0 the coarse network (:540), 2 tiles at zc; 1 the fine
-// network (:556), 6 tiles at zs
-template <int kPass, class Pol>
+// network (:556), kFineT / 32 tiles at zs (6, or 4 with 64 importance samples)
+template <int kPass, class Pol, int kFineT = kSf>
 HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L, const Ray& r, int lane, Pol& pol) {
   const int p = lane & 31, h = lane >> 5;
-  for (int tau = 0; tau < (kPass ? kSf : kSc) / 32; ++tau) {
+  for (int tau = 0; tau < (kPass ? kFineT : kSc) / 32; ++tau) {
     const float* P = opaque_ptr(kPass ? f.Pf : f.Pc);
+    // (the 4-tile fine pass only: the staged grid sizes' address laundered per
+    // tile, so encode_tile's twelve per-lane LDS addresses are formed in the
+    // tile, not held in VGPRs across the loop -- with them hoisted one value
+    // was reloaded from scratch in every fine tile; now none is.  The 6-tile
+    // instantiations are untouched.)
+    if constexpr (kPass && kFineT != kSf) {
+      int zero = 0;
+      asm volatile("" : "+s"(zero));
+      gsl += zero;
+    }
     const int q = 32 * tau + p;
     float pt[3];
     ray_point(r, L[(kPass ? kFZs : kFZc) + q], pt);
@@ -142,8 +160,10 @@ HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L,
 }
 
 // render_fwd_kernel's policy: features and masks into the feature cache (where
-// there is one), whose coarse tiles are the twins; raw to global memory
-template <bool kLoss>
+// there is one), whose coarse tiles are the twins; raw to global memory.
+// kSfT: the ray's fine samples, the stride of the caller's fine_src and raw_f
+// (the cache's tile index stays pass * 2 + tau)
+template <bool kLoss, int kSfT>
 struct TrainTiles {
   static constexpr bool kMasks = true;
   const RenderK& k;
@@ -151,7 +171,7 @@ struct TrainTiles {
   const uint8_t* srcl;   // kLoss: the samples' origins in LDS
   HN_DEV const float* twins() const { return k.feat ? k.feat + (size_t)ray * HN_RENDER_FEAT_PER_RAY : nullptr; }
   // (kLoss: from the LDS copy -- no global round trip ahead of each tile's gathers)
-  HN_DEV int origin(int q) const { return kLoss ? (int)srcl[q] : (int)k.fine_src[ray * kSf + q]; }
+  HN_DEV int origin(int q) const { return kLoss ? (int)srcl[q] : (int)k.fine_src[ray * kSfT + q]; }
   HN_DEV bool skip_dead(int pass) const { return k.skip_dead && (pass ? k.noise_f : k.noise_c) == nullptr; }
   HN_DEV void save_feat(int pass, int tau, int lane, const f32x16& feat) const {
     if (k.feat) store_feat(k.feat, ray, pass * (kSc / 32) + tau, lane, feat, k.feat_nt != 0);
@@ -160,7 +180,7 @@ struct TrainTiles {
     if (k.feat) store_masks(k.feat, ray, pass * (kSc / 32) + tau, lane, m, k.feat_nt != 0);
   }
   HN_DEV void save_raw(int pass, int q, const float4& o4) const {
-    *reinterpret_cast<float4*>(pass ? k.raw_f + (ray * kSf + q) * 4 : k.raw_c + (ray * kSc + q) * 4) = o4;
+    *reinterpret_cast<float4*>(pass ? k.raw_f + (ray * kSfT + q) * 4 : k.raw_c + (ray * kSc + q) * 4) = o4;
   }
 };
 
@@ -194,10 +214,15 @@ HN_DEV void composite_pass(const RenderK& k, int64_t ray, float* rawb, const flo
 // raw and marks into the backward's workspace (the binned schedule then
 // launches no pre-pass).  Both passes' composites sit outside the tile loops.
 // kLoss = false compiles to the forward without any of it.
-template <bool kLoss>
+// kNiT: the importance samples, kNi or kNi64 -- a compile-time shape (the fine
+// composite's samples per lane, the fine tile loop, the merge network's
+// depth), so the 64 + 128 instantiations are the code they were before the
+// second shape.  The workspace's d raw keeps its 64 + 192 stride for both.
+template <bool kLoss, int kNiT>
 __global__ __launch_bounds__(64 * kFwdBlockWaves)
 __attribute__((amdgpu_waves_per_eu(kFwdWavesPerSimd, kFwdWavesPerSimd)))
 void render_fwd_kernel(RenderK k) {
+  constexpr int kSfT = kSc + kNiT;   // the ray's fine samples
   __shared__ __attribute__((aligned(16))) float smem[kFwdBlockWaves * kFLds + kGsLds];
   // each wave's split-GEMM fragments one chunk ahead (FragRing, hn_mlp.h):
   // render_fwd_kernel 0.271 -> 0.266 ms, r05 ring (bitwise-identical outputs)
@@ -253,7 +278,7 @@ void render_fwd_kernel(RenderK k) {
   // kLoss: the samples' coarse origins kept in LDS for the marks (zsrc is free
   // after the merge), read beside the first fine tile's own look at them
   uint8_t* srcl = reinterpret_cast<uint8_t*>(zsrc);
-  TrainTiles<kLoss> pol{k, ray, srcl};
+  TrainTiles<kLoss, kSfT> pol{k, ray, srcl};
   pass_start(k.f.Pc, sh8, L, fring[wave], lane, false);
   pass_tiles<0>(k.f, gsl, fring[wave], L, r, lane, pol);
   lds_fence_wave();
@@ -278,27 +303,34 @@ void render_fwd_kernel(RenderK k) {
 
   // ---- importance sampling (:547-551) ----
   if (lane < kSc - 1) L[kFBins + lane] = .5f * (zc[lane + 1] + zc[lane]);
-  importance_sort(L, k.f.u + ray * kNi, k.fine_src + ray * kSf, lane);
+  importance_sort<kNiT>(L, k.f.u + ray * kNiT, k.fine_src + ray * kSfT, lane);
   {   // z_std of the samples as drawn (the sort reads zsrc only)
-    const float s0 = zsrc[kSc + lane], s1 = zsrc[kSc + 64 + lane];
-    const double mean = wave_sum((double)s0 + (double)s1) / kNi;
-    const double d0 = (double)s0 - mean, d1 = (double)s1 - mean;
-    const double var = wave_sum(d0 * d0 + d1 * d1) / kNi;
-    if (lane == 0) k.z_std[ray] = (float)sqrt(var);
+    if constexpr (kNiT == kNi) {
+      const float s0 = zsrc[kSc + lane], s1 = zsrc[kSc + 64 + lane];
+      const double mean = wave_sum((double)s0 + (double)s1) / kNi;
+      const double d0 = (double)s0 - mean, d1 = (double)s1 - mean;
+      const double var = wave_sum(d0 * d0 + d1 * d1) / kNi;
+      if (lane == 0) k.z_std[ray] = (float)sqrt(var);
+    } else {   // one sample per lane
+      const double s0 = (double)zsrc[kSc + lane];
+      const double d0 = s0 - wave_sum(s0) / kNiT;
+      const double var = wave_sum(d0 * d0) / kNiT;
+      if (lane == 0) k.z_std[ray] = (float)sqrt(var);
+    }
   }
-  for (int i = lane; i < kSf; i += 64) k.z_fine[ray * kSf + i] = zs[i];
+  for (int i = lane; i < kSfT; i += 64) k.z_fine[ray * kSfT + i] = zs[i];
 
   // ---- fine network (:556) ----
   pass_start(k.f.Pf, sh8, L, fring[wave], lane, true);
   if constexpr (kLoss) {
-    for (int i = lane; i < kSf; i += 64) srcl[i] = k.fine_src[ray * kSf + i];
+    for (int i = lane; i < kSfT; i += 64) srcl[i] = k.fine_src[ray * kSfT + i];
     lds_fence_wave();
   }
-  pass_tiles<1>(k.f, gsl, fring[wave], L, r, lane, pol);
+  pass_tiles<1, TrainTiles<kLoss, kSfT>, kSfT>(k.f, gsl, fring[wave], L, r, lane, pol);
   lds_fence_wave();
   CompOut fo;
-  composite_pass<kLoss, kSf / 64>(k, ray, rawb, zs, k.noise_f ? k.noise_f + ray * kSf : nullptr, kSf, r.dnorm,
-                                  nullptr, fo, lane);
+  composite_pass<kLoss, kSfT / 64>(k, ray, rawb, zs, k.noise_f ? k.noise_f + ray * kSfT : nullptr, kSfT, r.dnorm,
+                                   nullptr, fo, lane);
   if (lane == 0) {
 #pragma unroll
     for (int c = 0; c < 3; ++c) k.rgb[3 * ray + c] = fo.rgb[c];
@@ -307,8 +339,8 @@ void render_fwd_kernel(RenderK k) {
     k.sparsity[ray] = fo.entropy;
   }
   if constexpr (kLoss) {   // the fine pass's d raw and the ray's marks
-    const uint32_t nzf = draw_store_marks(rawb, k.draw + ((size_t)ray * (kSc + kSf) + kSc) * 4, kSf, lane);
-    const uint32_t su = scatter_marks(rawb, srcl, cmask, lane);
+    const uint32_t nzf = draw_store_marks(rawb, k.draw + ((size_t)ray * (kSc + kSf) + kSc) * 4, kSfT, lane);
+    const uint32_t su = scatter_marks<kSfT>(rawb, srcl, cmask, lane);
     if (lane == 0) store_fine_marks(k.uflags, ray, nzf, su);
   }
 }

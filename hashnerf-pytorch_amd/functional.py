@@ -236,6 +236,13 @@ class RenderState:
                  "fine_src", "feat", "wsb", "nbytes", "bwd_args", "skip_dead", "prepass_done", "__weakref__")
 
 
+def _fine_counts(cfg):
+    """(importance samples, fine samples per ray) of a render cfg: the widths
+    of u and of z_fine / raw_f / fine_src / noise_f / g_raw_f."""
+    ni = int(cfg.n_importance)
+    return ni, int(cfg.n_samples) + ni
+
+
 # workspace address -> the state of the last forward that ran the composite
 # backward into it (render_fwd(loss=...)): one workspace holds one ray batch's
 # d raw, so a later such forward on it invalidates the earlier state's
@@ -266,10 +273,19 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     ws = [w.contiguous() for w in ws]
     B = rays.shape[0]
     dev = rays.device
+    # the fine pass's tensors are sized by the cfg (64 + 128 samples, or 64 + 64)
+    ni, nf = _fine_counts(cfg)
+    for name, t, w in (("u", u, ni), ("noise_f", noise_f, nf)):
+        if t is not None and (t.numel() != B * w or (t.dim() and t.shape[-1] != w)):
+            raise ValueError(f"hashnerf_amd.render_fwd: {name} must be [{B}, {w}] for n_importance = {ni}, "
+                             f"got {tuple(t.shape)}")
+    if keep_feat and ni != 128 and L.lib().hn_render_scatter_mode(cfg, B) != 2:
+        raise ValueError("hashnerf_amd.render_fwd: n_importance = 64 trains on the binned backward only "
+                         "(hn_render_scatter_mode != 2 for this configuration)")
     e = lambda *s: torch.empty(s, dtype=torch.float32, device=dev)
     out = dict(rgb=e(B, 3), depth=e(B), acc=e(B), sparsity=e(B), rgb0=e(B, 3), depth0=e(B),
-               acc0=e(B), sparsity0=e(B), z_std=e(B), z_coarse=e(B, 64), z_fine=e(B, 192),
-               raw_c=e(B, 64, 4), raw_f=e(B, 192, 4))
+               acc0=e(B), sparsity0=e(B), z_std=e(B), z_coarse=e(B, 64), z_fine=e(B, nf),
+               raw_c=e(B, 64, 4), raw_f=e(B, nf, 4))
     a = L.HnRenderFwdArgs()
     a.n_rays = B
     for k, t in (("rays", rays), ("t_vals", t_vals), ("t_rand", t_rand), ("u", u),
@@ -279,7 +295,7 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     a.fine = L.make_mlp(ws[5:])
     for k, t in out.items():
         setattr(a, k, t.data_ptr())
-    fine_src = torch.empty((B, 192), dtype=torch.uint8, device=dev)
+    fine_src = torch.empty((B, nf), dtype=torch.uint8, device=dev)
     a.fine_src = fine_src.data_ptr()
     # hash features of every evaluated point, kept for the backward only
     # when a gradient will be taken (inference skips the 32 KB/ray store)
@@ -367,6 +383,10 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     next_batch.out once this call's launches have run."""
     B = st.rays.shape[0]
     dev = st.rays.device
+    g_raw_f = grads.get("g_raw_f")
+    if g_raw_f is not None and g_raw_f.numel() != st.raw_f.numel():
+        raise ValueError(f"hashnerf_amd.render_bwd: g_raw_f must be {tuple(st.raw_f.shape)} (the cfg's "
+                         f"n_importance = {_fine_counts(st.cfg)[0]}), got {tuple(g_raw_f.shape)}")
     if prepass_done:
         done = getattr(st, "prepass_done", None)
         if done is None:
@@ -516,7 +536,7 @@ def zeros_like_all(ts):
 
 
 class RenderRaysFn(torch.autograd.Function):
-    """Inputs: rays [B,11], t_vals [64], t_rand [B,64]|None, u [B,128],
+    """Inputs: rays [B,11], t_vals [64], t_rand [B,64]|None, u [B,cfg.n_importance],
     noise_c/noise_f |None, table, 5 coarse + 5 fine NeRFSmall weights.
     Outputs: rgb, depth, acc, sparsity, rgb0, depth0, acc0, sparsity0, z_std, raw."""
 

@@ -82,6 +82,32 @@ def bbox_for_blender(c2ws: Sequence[torch.Tensor], H: int, W: int, focal: float,
     return lo - 1.0, hi + 1.0
 
 
+def bbox_for_llff(poses, hwf, near: float = 0., far: float = 1.):
+    """bbox.py:44-75: min/max over the NDC rays (get_ndc_rays at near plane
+    1.0) of the 4 image corners of every pose ([n, 3, 4+]) at near and far,
+    padded by (0.1, 0.1, 0.0001).  The directions are formed for the whole
+    H x W grid with the reference's ops (ray_util.py:20-25, :48-49), so the
+    box is the reference's bit for bit."""
+    H, W, focal = hwf
+    H, W = int(H), int(W)
+    j, i = torch.meshgrid(torch.linspace(0, H - 1, H), torch.linspace(0, W - 1, W), indexing="ij")
+    directions = torch.stack([(i - W / 2) / focal, -(j - H / 2) / focal, -torch.ones_like(i)], -1)
+    corners = torch.tensor([0, W - 1, H * W - W, H * W - 1])
+    lo = torch.full((3,), 100.)
+    hi = torch.full((3,), -100.)
+    poses = poses.detach().cpu().float() if torch.is_tensor(poses) else torch.FloatTensor(np.asarray(poses))
+    for pose in poses:
+        rays_d = directions @ pose[:3, :3].T
+        rays_d = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
+        rays_o = pose[:3, -1].expand(rays_d.shape)
+        rays_o, rays_d = get_ndc_rays(H, W, focal, 1.0, rays_o.reshape(-1, 3)[corners], rays_d.reshape(-1, 3)[corners])
+        for pts in (rays_o + near * rays_d, rays_o + far * rays_d):
+            lo = torch.minimum(lo, pts.min(0).values)
+            hi = torch.maximum(hi, pts.max(0).values)
+    pad = torch.tensor([0.1, 0.1, 0.0001])
+    return lo - pad, hi + pad
+
+
 def blender_cameras(n: int = 100, radius: float = 4.0):
     """Synthetic nerf-synthetic-style training cameras: poses on the upper
     hemisphere (elevation -30 / -60 deg alternating), as SURVEY 8(d)."""

@@ -4,7 +4,7 @@ raw2outputs, sample_pdf, run_network, batchify, render_path) on HIP kernels.
 ``render_rays`` dispatches to the fused forward/backward kernels
 (``functional.RenderRaysFn``) whenever the configuration is the HashNeRF one
 (NetworkQuery over a 16-level HashEmbedder + SH, two NeRFSmall nets, 64+128
-samples with view directions); otherwise it composes the standalone HIP ops
+or 64+64 samples with view directions); otherwise it composes the standalone HIP ops
 exactly like the reference composes eager ops.  There is no CPU path.
 """
 from __future__ import annotations
@@ -116,7 +116,7 @@ def _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, n
     e, ed = network_query_fn.embed_fn, network_query_fn.embeddirs_fn
     return (isinstance(e, HashEmbedder) and e.n_levels == 16 and isinstance(ed, SHEncoder)
             and ed.degree == 4 and isinstance(network_fn, NeRFSmall)
-            and isinstance(network_fine, NeRFSmall) and N_samples == 64 and N_importance == 128
+            and isinstance(network_fine, NeRFSmall) and N_samples == 64 and N_importance in (64, 128)
             and ray_batch.shape[-1] > 8)
 
 
@@ -127,7 +127,15 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
     L.require_device(ray_batch)
     B = ray_batch.shape[0]
     dev = ray_batch.device
+    cfg = None
     if _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine):
+        cfg = HF.make_render_cfg(network_query_fn.embed_fn.grid(), white_bkgd, lindisp, perturb > 0.,
+                                 n_importance=N_importance)
+        # 64 importance samples (the LLFF configurations): fused on the binned
+        # backward schedule only; elsewhere the standalone ops, as before
+        if N_importance != 128 and L.lib().hn_render_scatter_mode(cfg, B) != 2:
+            cfg = None
+    if cfg is not None:
         emb = network_query_fn.embed_fn
         t_vals = _linspace_cached(N_samples, dev)
         t_rand = _draw((B, N_samples), dev, pytest, torch.rand) if perturb > 0. else None
@@ -144,7 +152,6 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
             rn = (lambda s, device: torch.randn(s, device=device))
             noise_c = _draw((B, N_samples), dev, pytest, rn) * raw_noise_std
             noise_f = _draw((B, N_samples + N_importance), dev, pytest, rn) * raw_noise_std
-        cfg = HF.make_render_cfg(emb.grid(), white_bkgd, lindisp, perturb > 0.)
         (rgb, depth, acc, sp, rgb0, depth0, acc0, sp0, z_std, raw) = HF.render_rays_fused(
             cfg, ray_batch, t_vals, t_rand, u, noise_c, noise_f, emb.table, network_fn.weights(),
             network_fine.weights())
@@ -251,7 +258,8 @@ def _image_ineligible(kw) -> Optional[str]:
     if not _fusable(np.empty((0, 11)), kw.get("network_fn"), kw.get("network_query_fn"), kw.get("N_samples"),
                     kw.get("N_importance", 0), kw.get("network_fine")):
         return "not the fused HashNeRF configuration (16-level hash grid + SH, two NeRFSmall nets, 64 + 128 samples)"
-    for why, bad in (("perturb != 0", kw.get("perturb", 0.) != 0.),
+    for why, bad in (("N_importance != 128", kw.get("N_importance", 0) != 128),
+                     ("perturb != 0", kw.get("perturb", 0.) != 0.),
                      ("raw_noise_std != 0", kw.get("raw_noise_std", 0.) != 0.),
                      ("ndc rays", bool(kw.get("ndc", True))),
                      ("no view directions (use_viewdirs=False)", not kw.get("use_viewdirs", False)),
@@ -270,8 +278,8 @@ def render_image(H, W, K, c2w, **render_kwargs):
     [n, 3, 4] (or [.., 4, 4]) poses, all rendered in that launch; returns rgb
     [(n,) H, W, 3], depth and acc [(n,) H, W].  Raises ValueError, naming the
     reason, for a configuration the kernel does not cover: anything but the
-    fused HashNeRF configuration, perturb, raw noise, ndc, no view directions,
-    c2w_staticcam or retraw."""
+    fused HashNeRF configuration, N_importance != 128, perturb, raw noise, ndc,
+    no view directions, c2w_staticcam or retraw."""
     why = _image_ineligible(render_kwargs)
     if why is not None:
         raise ValueError(f"hashnerf_amd.render_image: not eligible: {why}")

@@ -775,7 +775,10 @@ class Trainer:
         a = self.args
         self._cfg = HF.make_render_cfg(self.embed_fn.grid(), bool(kw.get("white_bkgd", False)),
                                        bool(kw.get("lindisp", False)), kw.get("perturb", 0.) > 0.,
-                                       dense_bwd=self.dense_bwd)
+                                       n_importance=kw["N_importance"], dense_bwd=self.dense_bwd)
+        if kw["N_importance"] != 128 and HF.L.lib().hn_render_scatter_mode(self._cfg, a.N_rand) != 2:
+            raise NotImplementedError("Trainer(mode='explicit') at N_importance = 64 needs the binned backward "
+                                      "schedule (hn_render_scatter_mode == 2 for this grid and N_rand)")
         self._t_vals = _linspace_cached(kw["N_samples"], self.device)
         self._ws = nf.weights() + nfine.weights()
         table = self.embed_fn.table
@@ -934,7 +937,15 @@ class Trainer:
         # composite backward itself (d raw and the marks left in the workspace)
         # and the backward launches no pre-pass
         fold = self.fuse_prepass and self.fuse_loss and self._binned and self.world == 1
-        out, st = HF.render_fwd(self._cfg, rays, self._t_vals, t_rand, u, None, None, table, self._ws, True,
+        # raw_noise_std (the LLFF configurations train with 1.0): render_rays' two
+        # randn draws (run_nerf_helpers.py:599-606), coarse then fine
+        noise_c = noise_f = None
+        std = float(self.kw_train.get("raw_noise_std", 0.) or 0.)
+        if std > 0.:
+            kw = self.kw_train
+            noise_c = torch.randn((rays.shape[0], kw["N_samples"]), device=self.device) * std
+            noise_f = torch.randn((rays.shape[0], kw["N_samples"] + kw["N_importance"]), device=self.device) * std
+        out, st = HF.render_fwd(self._cfg, rays, self._t_vals, t_rand, u, noise_c, noise_f, table, self._ws, True,
                                 wsb=self._rws, weights_packed=self._pk is not None and self._pk == self._pack_key(),
                                 skip_dead_color=(not self._cfg.dense_bwd) and self._binned,
                                 loss=dict(target=target, world=self.world, sparse_w=a.sparse_loss_weight)

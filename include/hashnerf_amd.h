@@ -139,11 +139,23 @@ int32_t hn_sample_pdf(const float* bins, const float* weights, const float* u,
 /* ---- fused render_rays (run_nerf_helpers.py:464-574) ---------------------
  * One kernel for the whole forward of a ray batch (coarse 64 -> composite ->
  * sample_pdf 128 -> sort -> fine 192 -> composite) and one for its backward.
- * Hash grid must have L=16, F=2; N_samples=64, N_importance=128. */
+ * Hash grid must have L=16, F=2; N_samples=64; N_importance=128, or 64 (the
+ * LLFF configurations: sample_pdf 64 -> sort -> fine 128).  Below, Ni =
+ * n_importance and Sf = 64 + Ni: the caller's per-ray tensors are sized by the
+ * cfg (u [B][Ni]; noise_f, z_fine, fine_src [B][Sf]; raw_f, g_raw_f
+ * [B][Sf][4]; the sizes written at the fields are those of Ni = 128), `feat`
+ * keeps HN_RENDER_FEAT_PER_RAY per ray (opaque; the tail a 4-tile fine pass
+ * does not use is not written), and hn_render_workspace_bytes(Ni = 64) <=
+ * that of Ni = 128.  Ni = 64 trains on the binned backward only: where
+ * hn_render_scatter_mode is not 2 (scatter = 1, T > 22, the box-geometry
+ * fallback), hn_render_fwd with feat != NULL and hn_render_bwd return
+ * HN_E_SHAPE before any launch; the inference forward (feat == NULL) runs for
+ * every T.  The whole-image kernel is 64 + 128 only: hn_render_image(_variant)
+ * return HN_E_SHAPE and hn_render_image_workspace_bytes 0 for Ni = 64. */
 typedef struct hn_render_cfg {
   hn_grid grid;
   int32_t n_samples;      /* 64 */
-  int32_t n_importance;   /* 128 */
+  int32_t n_importance;   /* 128 or 64 */
   int32_t white_bkgd;
   int32_t lindisp;
   int32_t perturb;        /* 1: stratified jitter from t_rand */
