@@ -73,6 +73,16 @@ class HnImageArgs(C.Structure):
 
 
 IMAGE_VARIANTS = {"reencode": 1, "row_major": 2}    # hn_render_image_variant's bits
+FWD_FORMS = {"auto": 0, "ring": 1, "resident": 2}   # hn_render_fwd_form's forms
+
+
+def fwd_form(form) -> int:
+    """A render_fwd form, by name or number, as hn_render_fwd_form's int; anything
+    else is refused here, on the host."""
+    v = FWD_FORMS.get(form, form) if isinstance(form, str) else form
+    if isinstance(v, bool) or not isinstance(v, int) or v not in FWD_FORMS.values():
+        raise ValueError(f"hashnerf_amd.render_fwd: form must be one of {sorted(FWD_FORMS)} or 0, 1, 2, got {form!r}")
+    return v
 
 
 class HnRadamTensor(C.Structure):
@@ -175,6 +185,9 @@ SIGNATURES = {
     "hn_render_scatter_mode": (C.c_int32, [C.POINTER(HnRenderCfg), C.c_int64]),
     "hn_render_fwd": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderFwdArgs), _P,
                                   C.c_size_t, _P]),
+    "hn_render_fwd_form": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderFwdArgs), C.c_int32, _P,
+                                       C.c_size_t, _P]),
+    "hn_render_fwd_pick": (C.c_int32, [C.c_int64, C.POINTER(C.c_int32)]),
     "hn_render_bwd": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                   C.c_size_t, _P]),
     "hn_render_image_workspace_bytes": (C.c_size_t, [C.POINTER(HnRenderCfg)]),

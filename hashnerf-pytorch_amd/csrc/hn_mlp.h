@@ -71,12 +71,15 @@ static_assert(W_END == HN_MLP_PARAMS, "param count");
 // against 0.314 ms for render_fwd_kernel, identical results), or, with a
 // FragRing source (the render forward, round 5), read from the wave's LDS slot
 // that a DMA filled during the previous chunk (0.271 -> 0.266 ms, no registers
-// held).  f32: one group ahead.  The scheduling barrier stops hipcc from
-// hoisting all loads (register blowup).
+// held), or, with a FragRes source (the render forward's resident form), from
+// the workgroup's LDS copy of the region where it has one.  f32: one group
+// ahead.  The scheduling barrier stops hipcc from hoisting all loads (register
+// blowup).
 // Where a GEMM's packed A fragments come from (the packed buffer in global
 // memory: frag_load).
 struct FragGlobal {
   static constexpr bool kRing = false;
+  static constexpr int kLdsEnd = 0;   // no region is read from LDS
   const float* P;
   HN_DEV f32x4 operator()(int off, int lane) const { return frag_load(P, off, lane); }
 };
@@ -106,9 +109,24 @@ constexpr int fwd_next_off(int r, int ob, int c) {
 // net's first chunk in the slot before its tiles.
 struct FragRing {
   static constexpr bool kRing = true;
+  static constexpr int kLdsEnd = 0;
   const float* P;
   float* slot;   // LDS, this wave's 768 floats
   HN_DEV f32x4 operator()(int off, int lane) const { return frag_load(P, off, lane); }
+};
+// The sigma net resident (the render forward's 16-wave form): the regions below
+// G_F2G -- R_F0 and R_F1, the packed net's first kFragResFloats floats, every
+// tile's 8 chunks -- are read from a copy of them the workgroup holds in LDS,
+// as packed, at compile-time offsets: no vmcnt wait, no refill.  The colour
+// regions (only tiles with density run them) are loaded at use, as FragGlobal.
+constexpr int kFragResFloats = G_F2G;
+struct FragRes {
+  static constexpr bool kRing = false;
+  static constexpr int kLdsEnd = kFragResFloats;   // region offsets below this are read from res
+  const float* P;
+  const float* res;   // LDS, the workgroup's P[0 .. kFragResFloats)
+  HN_DEV f32x4 operator()(int off, int lane) const { return frag_load(P, off, lane); }
+  HN_DEV f32x4 lds(int off, int lane) const { return *reinterpret_cast<const f32x4*>(res + off + 4 * lane); }
 };
 HN_DEV void ring_fill(const float* P, float* slot, int off, int lane) {
   int so = off * 4;
@@ -133,7 +151,10 @@ template <int R, typename BF, typename Src>
 HN_DEV f32x16 gemm_src(const Src& src, int ob, f32x16 acc, int lane, BF bval) {
   constexpr int KS = kRegKS[R], NS = reg_ns(R), GPO = reg_gpo(R), OFF = reg_off(R);
   // fragment group g of this block (frag_load: scalar offsets, hn_common.h)
-  auto ld = [&](int g) { return src(OFF + (ob * GPO + g) * 256, lane); };
+  auto ld = [&](int g) {
+    if constexpr (OFF < Src::kLdsEnd) return src.lds(OFF + (ob * GPO + g) * 256, lane);   // a resident region
+    else return src(OFF + (ob * GPO + g) * 256, lane);
+  };
   if constexpr (NS > 0) {        // split-f32, fragments loaded at use
 #pragma unroll
     for (int c = 0; c < KS / 8; ++c) {

@@ -14,6 +14,8 @@
 
 #include <math.h>
 
+#include <atomic>
+
 namespace hn {
 
 // Composite backward pre-pass of both schedules (raw2outputs backward,
@@ -344,10 +346,51 @@ extern "C" int32_t hn_device_faults(int32_t* faults, int32_t clear) {
   return hip_status(hipMemcpyToSymbol(HIP_SYMBOL(g_hn_fault), &zero, sizeof(int32_t)));
 }
 
+// The current device's compute units, asked once per device (0: not known)
+static int device_cus() {
+  static std::atomic<int> cached[64];
+  int dev = 0;
+  if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 0;
+  int n = cached[dev].load(std::memory_order_relaxed);
+  if (n == 0) {
+    if (hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess || n < 0) n = 0;
+    cached[dev].store(n, std::memory_order_relaxed);
+  }
+  return n;
+}
+// Which form of render_fwd_kernel a batch runs (hn_render_fwd.h; identical
+// bits, so the choice is free).  The resident form gives a CU to 16 rays, the
+// ring form spreads 4-ray workgroups over every CU: resident only where its
+// workgroups fill the device, ceil(n_rays / 16) >= CUs.
+static int fwd_pick_form(int64_t n_rays, int cus) {
+  return cus > 0 && (n_rays + kFwdResWaves - 1) / kFwdResWaves >= cus ? 2 : 1;
+}
+template <bool kLoss, int kNiT>
+static void launch_fwd(bool res, int64_t n_rays, hipStream_t s, const RenderK& k) {
+  const int bw = fwd_block_waves(res);
+  const dim3 grid((unsigned)((n_rays + bw - 1) / bw)), block(64 * bw);
+  if (res)
+    hipLaunchKernelGGL((render_fwd_kernel<kLoss, kNiT, true>), grid, block, 0, s, k);
+  else
+    hipLaunchKernelGGL((render_fwd_kernel<kLoss, kNiT, false>), grid, block, 0, s, k);
+}
+
+extern "C" int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus) {
+  const int n = device_cus();
+  if (cus) *cus = n;
+  return fwd_pick_form(n_rays, n);
+}
+
 extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_args* a,
                                  void* workspace, size_t ws_bytes, void* stream) {
+  return hn_render_fwd_form(cfg, a, 0, workspace, ws_bytes, stream);
+}
+
+extern "C" int32_t hn_render_fwd_form(const hn_render_cfg* cfg, const hn_render_fwd_args* a, int32_t form,
+                                      void* workspace, size_t ws_bytes, void* stream) {
   int32_t st = check_cfg(cfg);
   if (st) return st;
+  if (form < 0 || form > 2) return HN_E_SHAPE;
   if (!a) return HN_E_NULL;
   if (a->n_rays < 0) return HN_E_SHAPE;
   if (a->n_rays == 0) return HN_OK;
@@ -394,7 +437,7 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
   k.draw = nullptr;
   k.uflags = nullptr;
   k.stamp = nullptr;
-  const unsigned blocks = (unsigned)((a->n_rays + kFwdBlockWaves - 1) / kFwdBlockWaves);
+  const bool res = (form ? form : fwd_pick_form(a->n_rays, device_cus())) == 2;
   if (a->loss) {
     const WsDraw w = ws_draw(workspace, a->n_rays);
     k.ltarget = a->loss->target;
@@ -404,20 +447,20 @@ extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_a
     k.uflags = w.uflags;
     k.stamp = ws_stamp(w.lmeta);
     if (ni64)
-      hipLaunchKernelGGL((render_fwd_kernel<true, kNi64>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+      launch_fwd<true, kNi64>(res, a->n_rays, s, k);
     else
-      hipLaunchKernelGGL((render_fwd_kernel<true, kNi>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+      launch_fwd<true, kNi>(res, a->n_rays, s, k);
   } else if (ni64) {
-    hipLaunchKernelGGL((render_fwd_kernel<false, kNi64>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+    launch_fwd<false, kNi64>(res, a->n_rays, s, k);
   } else {
-    hipLaunchKernelGGL((render_fwd_kernel<false, kNi>), dim3(blocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+    launch_fwd<false, kNi>(res, a->n_rays, s, k);
   }
   return hip_status(hipGetLastError());
 }
 
 // Workspace of hn_render_image: both nets' packed weights | one slot per wave of
 // the persistent grid (its current ray's two coarse feature tiles)
-static size_t image_ws_floats() { return (size_t)2 * G_END + (size_t)kImgBlocks * kFwdBlockWaves * kImgSlotFloats; }
+static size_t image_ws_floats() { return (size_t)2 * G_END + (size_t)kImgBlocks * kImgBlockWaves * kImgSlotFloats; }
 
 extern "C" size_t hn_render_image_workspace_bytes(const hn_render_cfg* cfg) {
   return check_image_cfg(cfg) ? 0 : image_ws_floats() * sizeof(float);
@@ -454,7 +497,7 @@ extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_im
   k.poses = a->poses;
   k.slots = (variant & kImgReencode) ? nullptr : (float*)workspace + 2 * (size_t)G_END;
   k.rgb = a->rgb; k.depth = a->depth; k.acc = a->acc; k.rays = a->rays;
-  hipLaunchKernelGGL(render_image_kernel, dim3(kImgBlocks), dim3(64 * kFwdBlockWaves), 0, s, k);
+  hipLaunchKernelGGL(render_image_kernel, dim3(kImgBlocks), dim3(64 * kImgBlockWaves), 0, s, k);
   return hip_status(hipGetLastError());
 }
 

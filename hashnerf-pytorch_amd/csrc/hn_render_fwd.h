@@ -2,7 +2,8 @@
 // batch (run_nerf_helpers.py:464-574), one wave64 per ray, 4 waves per SIMD.
 // Coarse z (linspace + stratified jitter) -> 2 coarse tiles of 32 points
 // (hash-encode 16 levels + NeRFSmall on MFMA, the weight fragments through a
-// per-wave LDS ring) -> composite -> sample_pdf 128 -> merge of the sorted
+// per-wave LDS ring, or the sigma nets resident in LDS: the two forms below)
+// -> composite -> sample_pdf 128 -> merge of the sorted
 // runs (192) -> 6 fine tiles (a coarse sample's features reused) ->
 // composite.  Saves each tile's features and ReLU masks for the backward,
 // except (skip_dead) those of fine tiles without density.
@@ -35,16 +36,33 @@ constexpr int kFZc = 0, kFZsrc = 64, kFZs = 256, kFRaw = 448, kFW = 1216, kFBins
 // CUs (3 waves: 0.427 ms, a 1/3-occupied second round; 4: 0.418 ms)
 constexpr int kFwdWavesPerSimd = 4;
 
-// (Round 4 measured 16-wave workgroups with each net's forward weight
-// fragments staged in LDS instead of streamed from L2 per tile: the MLP phase
-// ran ~3x faster but the gathers of 16 waves in step ~2.3x slower,
-// render_fwd_kernel 0.294 vs 0.281 ms, and staggering half of the waves made it
-// 0.301-0.313 ms; profiles/r04/r04e, r04f.)
-constexpr int kFwdBlockWaves = kFwdWaves;
+// Two forms of render_fwd_kernel, bit for bit the same results (the MFMA
+// products and their order are the same; only where a GEMM's A fragments come
+// from differs):
+//   ring (kRes = false): 4-wave workgroups, every split-GEMM chunk through the
+//     wave's private 3-KiB LDS ring (FragRing), one buffer_load ... lds round
+//     trip per chunk;
+//   resident (kRes = true): 16-wave workgroups, one per CU.  The workgroup
+//     copies the sigma regions of both packed nets (Pc, Pf [0, kFragResFloats),
+//     2 x 24 KiB) into LDS once, ahead of the kernel's only barrier, and
+//     sigma_net.0 / .1 -- 8 of a tile's 22 chunks, and all of a tile without
+//     density -- read them there (FragRes): no vmcnt wait, no refill, no
+//     reload at the pass switch.  The colour net's chunks are loaded at use.
+//     LDS: 16 x kFLds + kGsLds + 2 x kFragResFloats floats = 143,744 B.
+// (Round 4's whole-net-in-LDS form, one net at a time with a reload and a
+// barrier at the pass switch, every tile 22 chunks, lost 0.294 to 0.281 ms:
+// the 16 waves marched in step; profiles/r04/r04e, r04f.)
+// hn_render_fwd picks the resident form where the batch fills the device with
+// 16-ray workgroups (fwd_pick_form, hn_render.hip).
+constexpr int kFwdBlockWaves = kFwdWaves;   // the ring form's workgroup
+constexpr int kFwdResWaves = 16;            // the resident form's
+constexpr int kFwdResRuns = 4;              // ... made of this many runs of consecutive rays (the note at `run`)
+constexpr int fwd_block_waves(bool res) { return res ? kFwdResWaves : kFwdBlockWaves; }
 
 // ---- the ray passes, shared with render_image_kernel -----------------------
-// L: the wave's kFLds floats (the map above), ring: its FragRing slot, gsl: the
-// block's staged grid sizes.  A policy Pol, every hook inline (pass: 0 coarse,
+// L: the wave's kFLds floats (the map above), ring: its FragRing slot (kRes:
+// the workgroup's resident sigma regions of the pass's net), gsl: the block's
+// staged grid sizes.  A policy Pol, every hook inline (pass: 0 coarse,
 // 1 fine, a constant at each call):
 //   kMasks           the tiles' ReLU masks are formed
 //   twins()          the ray's two stored coarse tiles (store_feat's layout), or null
@@ -60,11 +78,14 @@ HN_DEV float coarse_z(float t, float near, float far, int lindisp) {
 // A pass's prologue: color_net.0's SH half of the ray into LDS (the previous
 // pass's tiles have read theirs: in-order LDS), the net's first chunk into the
 // ring.  drain: the previous pass's last (unused) ring fill lands first.
+// kRes: there is no ring to start; the one wait per pass stays (the ray's
+// coarse tiles are stored before its fine pass loads the twins from them).
+template <bool kRes = false>
 HN_DEV void pass_start(const float* P, const float sh8[8], float* L, float* ring, int lane, bool drain) {
   c0sh_lds_store(opaque_ptr(P), sh8, L + kFC0, lane);
   lds_fence_wave();
   if (drain) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  fwd_ring_start(P, ring, lane);
+  if constexpr (!kRes) fwd_ring_start(P, ring, lane);
 }
 
 // The coarse twin src of a fine sample: its features from the ray's stored
@@ -101,7 +122,7 @@ HN_DEV void importance_sort(float* L, const float* u, uint8_t* org, int lane) {
 
 // A pass's tiles: kPass 0 the coarse network (:540), 2 tiles at zc; 1 the fine
 // network (:556), kFineT / 32 tiles at zs (6, or 4 with 64 importance samples)
-template <int kPass, class Pol, int kFineT = kSf>
+template <int kPass, class Pol, int kFineT = kSf, bool kRes = false>
 HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L, const Ray& r, int lane, Pol& pol) {
   const int p = lane & 31, h = lane >> 5;
   for (int tau = 0; tau < (kPass ? kFineT : kSc) / 32; ++tau) {
@@ -110,8 +131,9 @@ HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L,
     // tile, so encode_tile's twelve per-lane LDS addresses are formed in the
     // tile, not held in VGPRs across the loop -- with them hoisted one value
     // was reloaded from scratch in every fine tile; now none is.  The 6-tile
-    // instantiations are untouched.)
-    if constexpr (kPass && kFineT != kSf) {
+    // instantiations of the ring form are untouched; the resident form's take
+    // it too.)
+    if constexpr (kPass && (kFineT != kSf || kRes)) {
       int zero = 0;
       asm volatile("" : "+s"(zero));
       gsl += zero;
@@ -145,7 +167,8 @@ HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L,
     const bool dead_skip = pol.skip_dead(kPass);
     bool stored = kPass == 0 || !dead_skip;
     if (stored) pol.save_feat(kPass, tau, lane, feat);
-    mlp_fwd_tile_src<Pol::kMasks>(FragRing{P, ring}, feat, [&](int ob) { return c0sh_lds_load(L + kFC0, ob, lane); },
+    using Src = std::conditional_t<kRes, FragRes, FragRing>;
+    mlp_fwd_tile_src<Pol::kMasks>(Src{P, ring}, feat, [&](int ob) { return c0sh_lds_load(L + kFC0, ob, lane); },
                                   a, c2, lane, dead_skip, [&]() {
                                     if (!stored) pol.save_feat(kPass, tau, lane, feat);
                                     stored = true;
@@ -218,22 +241,40 @@ HN_DEV void composite_pass(const RenderK& k, int64_t ray, float* rawb, const flo
 // composite's samples per lane, the fine tile loop, the merge network's
 // depth), so the 64 + 128 instantiations are the code they were before the
 // second shape.  The workspace's d raw keeps its 64 + 192 stride for both.
-template <bool kLoss, int kNiT>
-__global__ __launch_bounds__(64 * kFwdBlockWaves)
+// kRes: the resident form (the note at kFwdResWaves).
+template <bool kLoss, int kNiT, bool kRes = false>
+__global__ __launch_bounds__(64 * fwd_block_waves(kRes))
 __attribute__((amdgpu_waves_per_eu(kFwdWavesPerSimd, kFwdWavesPerSimd)))
 void render_fwd_kernel(RenderK k) {
   constexpr int kSfT = kSc + kNiT;   // the ray's fine samples
-  __shared__ __attribute__((aligned(16))) float smem[kFwdBlockWaves * kFLds + kGsLds];
+  constexpr int kBW = fwd_block_waves(kRes);
+  __shared__ __attribute__((aligned(16))) float smem[kBW * kFLds + kGsLds];
   // each wave's split-GEMM fragments one chunk ahead (FragRing, hn_mlp.h):
-  // render_fwd_kernel 0.271 -> 0.266 ms, r05 ring (bitwise-identical outputs)
-  __shared__ __attribute__((aligned(16))) float fring[kFwdBlockWaves][768];
+  // render_fwd_kernel 0.271 -> 0.266 ms, r05 ring (bitwise-identical outputs);
+  // kRes: the array holds the workgroup's resident sigma regions instead, the
+  // coarse net's, then the fine net's (the same 768 floats per wave)
+  static_assert(2 * kFragResFloats % (4 * kFwdResWaves) == 0, "a whole dwordx4 share per wave");
+  __shared__ __attribute__((aligned(16))) float fring[kBW][kRes ? 2 * kFragResFloats / kFwdResWaves : 768];
   // the wave index (and with it the ray, its 11 floats and every per-ray
   // address) on the scalar unit: VGPR spills 45 -> 22, render_fwd_kernel
   // 0.296 -> 0.281 ms (r04e)
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int lane = threadIdx.x & 63;
-  float* gsl = smem + kFwdBlockWaves * kFLds;
+  float* gsl = smem + kBW * kFLds;
   stage_grid_sizes(k.f.g, gsl);
+  if constexpr (kRes) {
+    // every wave of the workgroup, those past the batch's end too: they return
+    // only after the barrier
+    constexpr int kN4 = kFragResFloats / 4;   // dwordx4 per net
+    const f32x4* srcc = reinterpret_cast<const f32x4*>(k.f.Pc);
+    const f32x4* srcf = reinterpret_cast<const f32x4*>(k.f.Pf);
+    f32x4* dst = reinterpret_cast<f32x4*>(&fring[0][0]);
+#pragma unroll
+    for (int i = 0; i < (2 * kN4 + 64 * kBW - 1) / (64 * kBW); ++i) {
+      const int j = i * 64 * kBW + (int)threadIdx.x;
+      if (j < 2 * kN4) dst[j] = j < kN4 ? srcc[j] : srcf[j - kN4];
+    }
+  }
   __syncthreads();
   // XCD-aware: workgroup b runs on XCD b % 8, so consecutive ray groups of a
   // spatially ordered batch go to one XCD and share its L2
@@ -242,7 +283,23 @@ void render_fwd_kernel(RenderK k) {
   // XCDs, or no XCD mapping at all, were no faster: 234.9 / 228.8 / 240.4 us
   // against 229.4 us -- the forward's per-XCD work is balanced already)
   const int64_t grp = nb % 8 == 0 ? (blockIdx.x % 8) * (nb / 8) + blockIdx.x / 8 : blockIdx.x;
-  const int64_t ray = grp * kFwdBlockWaves + wave;
+  int64_t ray = grp * kBW + wave;
+  if constexpr (kRes) {
+    // A CU runs its 16 rays from start to end, and a batch in spatial order
+    // gives consecutive rays alike amounts of work (tiles with density run
+    // the colour net): with 16 consecutive rays per workgroup the kernel
+    // waits for the CUs whose rays are all heavy.  So the workgroup takes
+    // kFwdResRuns runs of 4 consecutive rays (the ring form's group: they
+    // share table rows in the CU's cache), one from each quarter of its XCD's
+    // band of the batch.  Config 2, 4096 rays: render_fwd_kernel 0.2327 ms as
+    // 1 run of 16, 0.2216 as 4 runs of 4, 0.2242 as 16 single rays
+    // (profiles/r12/); the mean wave is resident for only ~3/4 of the launch.
+    constexpr int kW = kBW / kFwdResRuns;
+    const int s = wave / kW;
+    const int64_t run = nb % 8 == 0 ? (blockIdx.x % 8) * (nb / 8 * kFwdResRuns) + s * (nb / 8) + blockIdx.x / 8
+                                    : s * nb + blockIdx.x;
+    ray = run * kW + wave % kW;   // every ray below 16 nb once; those past the batch's end leave below
+  }
   if constexpr (kLoss) {
     // the stamp render_lists_kernel checks: d raw and marks of these n_rays follow
     if (blockIdx.x == 0 && threadIdx.x == 0) *k.stamp = stamp_word(k.B);
@@ -279,8 +336,11 @@ void render_fwd_kernel(RenderK k) {
   // after the merge), read beside the first fine tile's own look at them
   uint8_t* srcl = reinterpret_cast<uint8_t*>(zsrc);
   TrainTiles<kLoss, kSfT> pol{k, ray, srcl};
-  pass_start(k.f.Pc, sh8, L, fring[wave], lane, false);
-  pass_tiles<0>(k.f, gsl, fring[wave], L, r, lane, pol);
+  // the passes' fragment source: the wave's ring slot, or the net's resident regions
+  float* srcc = kRes ? &fring[0][0] : fring[wave];
+  float* srcf = kRes ? &fring[0][0] + kFragResFloats : fring[wave];
+  pass_start<kRes>(k.f.Pc, sh8, L, srcc, lane, false);
+  pass_tiles<0, TrainTiles<kLoss, kSfT>, kSf, kRes>(k.f, gsl, srcc, L, r, lane, pol);
   lds_fence_wave();
   CompOut co;
   composite_pass<kLoss, kSc / 64>(k, ray, rawb, zc, k.noise_c ? k.noise_c + ray * kSc : nullptr, kSc, r.dnorm, wts,
@@ -321,12 +381,12 @@ void render_fwd_kernel(RenderK k) {
   for (int i = lane; i < kSfT; i += 64) k.z_fine[ray * kSfT + i] = zs[i];
 
   // ---- fine network (:556) ----
-  pass_start(k.f.Pf, sh8, L, fring[wave], lane, true);
+  pass_start<kRes>(k.f.Pf, sh8, L, srcf, lane, true);
   if constexpr (kLoss) {
     for (int i = lane; i < kSfT; i += 64) srcl[i] = k.fine_src[ray * kSfT + i];
     lds_fence_wave();
   }
-  pass_tiles<1, TrainTiles<kLoss, kSfT>, kSfT>(k.f, gsl, fring[wave], L, r, lane, pol);
+  pass_tiles<1, TrainTiles<kLoss, kSfT>, kSfT, kRes>(k.f, gsl, srcf, L, r, lane, pol);
   lds_fence_wave();
   CompOut fo;
   composite_pass<kLoss, kSfT / 64>(k, ray, rawb, zs, k.noise_f ? k.noise_f + ray * kSfT : nullptr, kSfT, r.dnorm,

@@ -23,6 +23,8 @@ namespace hn {
 // 4 workgroups per CU (4 waves per SIMD, as the forward) on 256 CUs; a
 // compile-time count, so the workspace's size needs no device
 constexpr int kImgBlocks = 1024;
+// its workgroup: 4 waves and the ring, whichever form the training forward runs
+constexpr int kImgBlockWaves = kFwdWaves;
 constexpr int kImgSlotFloats = 2 * 1024;   // a wave's two coarse feature tiles (store_feat's layout)
 static_assert(kImgBlocks % 8 == 0, "one band of ray groups per XCD residue");
 // 2 x 2 pixel blocks per side of a tile of the ray order (16 x 16 pixels)
@@ -106,14 +108,14 @@ struct ImageTiles {
 
 HN_DEV float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
-__global__ __launch_bounds__(64 * kFwdBlockWaves)
+__global__ __launch_bounds__(64 * kImgBlockWaves)
 __attribute__((amdgpu_waves_per_eu(kFwdWavesPerSimd, kFwdWavesPerSimd)))
 void render_image_kernel(ImageK k) {
-  __shared__ __attribute__((aligned(16))) float smem[kFwdBlockWaves * kFLds + kGsLds + kImgPixLds];
-  __shared__ __attribute__((aligned(16))) float fring[kFwdBlockWaves][768];
+  __shared__ __attribute__((aligned(16))) float smem[kImgBlockWaves * kFLds + kGsLds + kImgPixLds];
+  __shared__ __attribute__((aligned(16))) float fring[kImgBlockWaves][768];
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
   const int lane0 = threadIdx.x & 63;
-  float* gsl = smem + kFwdBlockWaves * kFLds;
+  float* gsl = smem + kImgBlockWaves * kFLds;
   const float* pixl = gsl + kGsLds;
   stage_grid_sizes(k.f.g, gsl);
   if (threadIdx.x == 64) {
@@ -128,7 +130,7 @@ void render_image_kernel(ImageK k) {
     for (int i = 0; i < (int)(sizeof(ImagePix) / 4); ++i) gsl[kGsLds + i] = __uint_as_float(w[i]);
   }
   __syncthreads();
-  float* slot = k.slots ? k.slots + ((size_t)blockIdx.x * kFwdBlockWaves + wave) * kImgSlotFloats : nullptr;
+  float* slot = k.slots ? k.slots + ((size_t)blockIdx.x * kImgBlockWaves + wave) * kImgSlotFloats : nullptr;
 
   // ---- coarse z_vals (:514-536) and their mid points: near, far and t_vals
   // are the launch's, so every ray of the wave shares them ----
@@ -173,7 +175,7 @@ void render_image_kernel(ImageK k) {
       uint32_t view;
       if (x.variant & kImgRowMajor) {   // 4 consecutive pixels of the (view, row, column) order
         const uint32_t per_view = (uint32_t)x.H * (uint32_t)x.W;   // < 2^31: groups is
-        ray = (int64_t)grp * kFwdBlockWaves + wave;
+        ray = (int64_t)grp * kImgBlockWaves + wave;
         if (ray >= (int64_t)k.n_views * per_view) continue;
         view = (uint32_t)(ray / per_view);
         const uint32_t i = (uint32_t)(ray - (int64_t)view * per_view);

@@ -65,6 +65,10 @@ TIMER = KernelTimer()
 # z-values / raw outputs of the last call in LAST (no effect on results).
 DEBUG_KEEP = False
 LAST = {}
+# The form of render_fwd_kernel that render_fwd calls without a form= of their
+# own run (_lib.FWD_FORMS: "auto", the library's rule; "ring"; "resident" --
+# identical bits).  A/B measurements of a whole step set it.
+FWD_FORM = "auto"
 # When True, every render backward is followed by a check of the device fault
 # word (hn_device_faults: a blocking read).  The tests turn it on; trainers
 # check every Trainer.fault_check_every steps instead.
@@ -250,7 +254,7 @@ _PREPASS_ON_WS = {}
 
 
 def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_feat, wsb=None,
-               weights_packed=False, skip_dead_color=False, loss=None):
+               weights_packed=False, skip_dead_color=False, loss=None, form=None):
     """hn_render_fwd (run_nerf_helpers.py:464-574, forward).  Returns the
     output dict and a RenderState (None when keep_feat is False).  wsb: the
     caller's workspace (uint8, >= workspace_bytes; default a fresh one);
@@ -266,7 +270,12 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     of the training loss on the raw / z it still holds, and leaves d raw and
     the work marks in the workspace; the state's one render_bwd then takes
     the same loss with prepass_done=True and launches no pre-pass (bitwise
-    the same gradients; every output here is unchanged)."""
+    the same gradients; every output here is unchanged).
+    form (hn_render_fwd_form; None = FWD_FORM): "auto", "ring" (4-ray
+    workgroups, the weight fragments through per-wave LDS rings) or "resident"
+    (16-ray workgroups, both sigma nets held in LDS) -- identical bits; auto
+    takes the resident form where the batch fills the device (fwd_pick)."""
+    form = L.fwd_form(FWD_FORM if form is None else form)   # refused on the host, before any launch
     L.require_device(rays, t_vals, t_rand, u, noise_c, noise_f, table, *ws)
     rays, t_vals, t_rand, u, noise_c, noise_f = (L.contig(t) for t in (rays, t_vals, t_rand, u,
                                                                       noise_c, noise_f))
@@ -318,7 +327,7 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
         la.world, la.sparse_w = float(loss["world"]), float(loss["sparse_w"])
         a.loss = C.pointer(la)
     t0 = TIMER.begin("render_fwd")
-    L.check(L.lib().hn_render_fwd(cfg, a, L.ptr(wsb), nbytes, L.stream(dev)), "render_fwd")
+    L.check(L.lib().hn_render_fwd_form(cfg, a, form, L.ptr(wsb), nbytes, L.stream(dev)), "render_fwd")
     TIMER.end("render_fwd", t0)
     if DEBUG_KEEP:
         LAST.update({k: out[k] for k in ("z_coarse", "z_fine", "raw_c", "raw_f")})
@@ -509,6 +518,16 @@ def render_bins(cfg, n_rays: int):
     shift = C.c_int32(0)
     n = L.lib().hn_render_bins(cfg, n_rays, C.byref(shift))
     return int(n), int(shift.value)
+
+
+def fwd_pick(n_rays: int):
+    """(form, compute units): the form render_fwd's "auto" runs for n_rays on
+    the current device (hn_render_fwd_pick: "resident" where ceil(n_rays / 16)
+    reaches the device's compute units, else "ring"), and the count that rule
+    was stated against."""
+    cus = C.c_int32(0)
+    form = L.lib().hn_render_fwd_pick(int(n_rays), C.byref(cus))
+    return {v: k for k, v in L.FWD_FORMS.items()}[int(form)], int(cus.value)
 
 
 def render_bwd_owner(st: RenderState, bin_lo: int, bin_hi: int):

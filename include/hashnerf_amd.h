@@ -28,8 +28,9 @@ extern "C" {
  * where zero / NULL keeps the earlier behaviour: hn_render_fwd_args.loss,
  * hn_render_bwd_args.prepass_done and .next_batch (a caller built against the shorter structs
  * must zero-fill the args, as every caller of this ABI does), and the additive
- * entry points hn_sample_pool_ordered and hn_render_image (with its
- * hn_render_image_workspace_bytes and hn_render_image_variant). */
+ * entry points hn_sample_pool_ordered, hn_render_image (with its
+ * hn_render_image_workspace_bytes and hn_render_image_variant),
+ * hn_render_fwd_form and hn_render_fwd_pick. */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
 
@@ -532,6 +533,18 @@ size_t hn_render_workspace_bytes(const hn_render_cfg* cfg, int64_t n_rays);
 int32_t hn_render_scatter_mode(const hn_render_cfg* cfg, int64_t n_rays);
 int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
+/* hn_render_fwd with the form of its kernel chosen by the caller (additive
+ * under ABI 14; tests and A/B measurements), every output bitwise
+ * hn_render_fwd's: 1 = 4-ray workgroups, every weight fragment through a
+ * per-wave LDS ring; 2 = 16-ray workgroups that hold both nets' sigma layers
+ * resident in LDS; 0 = hn_render_fwd, which picks 2 where ceil(n_rays / 16)
+ * reaches the device's compute units and 1 below that.  Any other form:
+ * HN_E_SHAPE, before anything is launched. */
+int32_t hn_render_fwd_form(const hn_render_cfg* cfg, const hn_render_fwd_args* a, int32_t form,
+                           void* workspace, size_t ws_bytes, void* stream);
+/* The form (1 or 2) hn_render_fwd runs for n_rays on the current device;
+ * *cus (optional) = the compute units that rule was stated against. */
+int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus);
 int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
 
