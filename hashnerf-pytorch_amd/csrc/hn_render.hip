@@ -15,6 +15,7 @@
 #include <math.h>
 
 #include <atomic>
+#include <type_traits>
 
 namespace hn {
 
@@ -191,58 +192,94 @@ static int bwd_mode(const hn_render_cfg* c, int64_t n_rays) {
   return kModeSplit;
 }
 
+// A workspace is laid out by a running cursor, in floats from its base: take
+// n floats at an alignment, get their offset.  Regions cannot overlap and the
+// cursor's end is the size.
+struct WsCursor {
+  size_t at = 0;
+  size_t take(size_t n, size_t align = 1) {
+    const size_t o = (at + align - 1) & ~(align - 1);
+    at = o + n;
+    return o;
+  }
+};
+template <class T>
+static T* ws_at(void* workspace, size_t ofs) { return reinterpret_cast<T*>((float*)workspace + ofs); }
+
+// The render workspace of (schedule, n rays), offsets in floats: the one place
+// its layout is written down.  What the kernels index by themselves is tied
+// to it here: render_lists_kernel and the binned render_bwd_kernel find the
+// fine list 4 B behind B1K::lists and the scatter's 12 B behind that (a code
+// per 16-sample group), a ray's marks are one word, ovf_place_kernel's repack
+// writes both nets as [2][G_END], and ws_stamp's word lies within the counts.
+constexpr size_t kListC = 4, kListF = 12, kListS = 12;   // list entries per ray: coarse, fine, the scatter's
+constexpr size_t kListCounts = 8;                        // B1K::lmeta: 4 counts, then the stamp's words
+static_assert(kListC == kSc / 16 && kListF == kSf / 16 && kListS == kSf / 16 && kMarkB == sizeof(float) &&
+              kStampAt >= 4 && kStampAt + 3 <= (int)kListCounts, "the kernels' own offsets");
+static_assert(G_END % 4 == 0 && W_END % 4 == 0 && kDcRay % 4 == 0, "every float4 region is 16-byte aligned");
+struct WsLayout {
+  size_t Pc, Pf, slab, dfeat, draw, marks, lmeta, lc, lf, ls, dfeat_f, bins, total;
+};
+static WsLayout ws_layout(int mode, const BinGeom& bg, int64_t n_rays) {
+  const size_t n = n_rays > 0 ? (size_t)n_rays : 0;
+  const bool binned = mode == kModeSplit;
+  WsCursor c;
+  WsLayout w;
+  w.Pc = c.take(G_END);                                       // packed coarse net
+  w.Pf = c.take(G_END);                                       // packed fine net
+  w.slab = c.take((size_t)kBwdBlocks * kSlabSlots * W_END);   // dW slabs [256][4][9344]
+  w.dfeat = c.take(n * kDcRay);                               // coarse-pass feature grads [n][64][32]
+  w.draw = c.take(n * (kSc + kSf) * 4);                       // d raw [n][256][4]
+  w.marks = c.take(n * kMarkB / sizeof(float));               // unit marks [n][kMarkB] u8 (B1K::uflags)
+  w.lmeta = c.take(kListCounts);                              // the lists' counts, the training forward's stamp
+  w.lc = c.take(kListC * n);                                  // the lists' group codes: coarse (B1K::lists),
+  w.lf = c.take(kListF * n);                                  // fine,
+  w.ls = c.take(kListS * n);                                  // the scatter's (ScK::slist)
+  w.dfeat_f = c.take(binned ? n * kSf * 32 : 0, 4);           // binned: fine feature grads [n][6][1024]
+  w.bins = c.take(binned ? bg.floats : 0);                    // binned: the records and their book (bin_geom)
+  w.total = c.at;
+  return w;
+}
+
 // The backward's plan for (cfg, n_rays), host arithmetic only: the schedule,
 // and with it the workspace layout; for the binned schedule also the bin
 // geometry and scatter_bins_kernel's dynamic LDS (the bins' counters, then
 // the staging pool).
-// Workspace (floats): packed coarse + fine weights | dW slabs [256][4][9344] |
-// coarse-pass feature grads [n][64][32] | d raw [n][256][4] | unit marks
-// [n][4] u8, the lists' counts [8] (words 4-7: the training forward's stamp,
-// ws_stamp), the lists [(4 + 12 + 12) n] | binned: fine
-// feature grads [n][6][1024] (dfeat_f) and the records (bins; bin_geom).
 struct BwdPlan {
   int mode;          // kModeSplit (binned) or kModeAtomic
   BinGeom bg;        // binned only
   size_t sc_lds;     // binned only
-  size_t dfeat_f, bins, total;
-  size_t bytes() const { return total * sizeof(float); }
+  WsLayout ws;
+  size_t bytes() const { return ws.total * sizeof(float); }
 };
 static BwdPlan bwd_plan(const hn_render_cfg* cfg, int64_t n_rays) {
   BwdPlan p{};
   p.mode = bwd_mode(cfg, n_rays);
-  const size_t n = n_rays > 0 ? (size_t)n_rays : 0;
-  p.dfeat_f = (size_t)2 * G_END + (size_t)kBwdBlocks * kSlabSlots * W_END + n * kDcRay + n * (kSc + kSf) * 4 +
-              ((29 * n + 8 + 3) & ~(size_t)3);
-  p.bins = p.total = p.dfeat_f;
   if (p.mode == kModeSplit) {
     p.bg = bin_geom(cfg->grid.log2_hashmap_size, n_rays, cfg->bin_cap);
     p.sc_lds = (size_t)((p.bg.nbins + 3) & ~3) * 8 + (size_t)kStPool * 20;
-    p.bins = p.dfeat_f + n * kSf * 32;
-    p.total = p.bins + p.bg.floats;
   }
+  p.ws = ws_layout(p.mode, p.bg, n_rays);
   return p;
-}
-// Where the composite backward's results live in the workspace (the layout
-// above), for the pre-pass and for the training forward that replaces it.
-struct WsDraw {
-  float *slab, *dfeat, *draw;
-  uint8_t* uflags;
-  int32_t* lmeta;
-};
-static WsDraw ws_draw(void* workspace, int64_t n_rays) {
-  WsDraw w;
-  w.slab = (float*)workspace + 2 * (size_t)G_END;
-  w.dfeat = w.slab + (size_t)kBwdBlocks * kSlabSlots * W_END;
-  w.draw = w.dfeat + (size_t)n_rays * kDcRay;
-  w.uflags = reinterpret_cast<uint8_t*>(w.draw + (size_t)n_rays * (kSc + kSf) * 4);
-  // the work lists' counts (and the training forward's stamp) and the lists, after the marks
-  w.lmeta = reinterpret_cast<int32_t*>(w.uflags + kMarkB * (size_t)n_rays);
-  return w;
 }
 
 // The training forward's stamp: the 8-byte aligned word within lmeta[4..7]
 static unsigned long long* ws_stamp(int32_t* lmeta) {
   return reinterpret_cast<unsigned long long*>((reinterpret_cast<uintptr_t>(lmeta + kStampAt) + 7) & ~(uintptr_t)7);
+}
+
+// The overflow book of a call's records (the kernels derive it alike)
+static OvfBook host_ovf_book(float* bins, const BinGeom& bg, int64_t n_rays) {
+  const size_t nrec = bin_records(bg.nbins, bg.cap, n_rays);
+  return ovf_book(reinterpret_cast<uint32_t*>(bins + 4 * nrec), nrec, bg.nbins);
+}
+
+// The loss's upstream factors (hn_loss_bwd's with g_loss = 1): one definition
+// for the training forward and the pre-pass, which must agree bitwise
+static void loss_factors(float world, float sparse_w, int64_t n_rays, float& gm, float& sparse) {
+  const float g = 1.f;
+  gm = (g / world) / (float)(3 * n_rays);
+  sparse = g * sparse_w;
 }
 
 // scatter_bins_kernel's dynamic LDS fits beside its static LDS, read once
@@ -268,6 +305,20 @@ static int32_t check_table_step(const hn_render_cfg* cfg, const hn_render_bwd_ar
   if (!ts.p || !ts.m || !ts.v) return HN_E_NULL;
   if (a->table_live && (a->table_live_levels < 0 || a->table_live_levels > cfg->grid.n_levels || T < 6))
     return HN_E_SHAPE;
+  return HN_OK;
+}
+
+// A backward's TV term (a->tv given): its gradient's factor, make_tv, the
+// grid's levels and T; rec_fit: its records fit the binned scatter's overflow
+// lists (ovf_per_block: every cube <= kTvRecMaxCube)
+static int32_t check_tv(const hn_render_cfg* cfg, const hn_render_bwd_args* a, TvK& tvk, bool& rec_fit) {
+  if (!a->g_tv) return HN_E_NULL;
+  int nbf, nbb;
+  if (int32_t st = make_tv(a->tv, tvk, nbf, nbb)) return st;
+  if (a->tv->n_levels != cfg->grid.n_levels || a->tv->log2_hashmap_size != cfg->grid.log2_hashmap_size)
+    return HN_E_SHAPE;
+  rec_fit = a->tv->n_levels <= 16;
+  for (int l = 0; l < a->tv->n_levels && rec_fit; ++l) rec_fit = a->tv->cube[l] <= kTvRecMaxCube;
   return HN_OK;
 }
 
@@ -315,12 +366,11 @@ static void launch_owner(const BinR& r, const BinGeom& bg, int n_bins, hipStream
 }
 
 // What hn_render_fwd and hn_render_image share of their kernels' arguments; the
-// nets' packed copies at the head of the workspace are made here unless given
+// nets' packed copies (Pc, Pf: their workspace's) are made here unless given
 static int32_t field_args(const hn_render_cfg* cfg, const float* t_vals, const float* u, const float* table,
                           const hn_mlp& coarse, const hn_mlp& fine, int32_t weights_packed, void* workspace,
-                          hipStream_t s, FieldK& f) {
-  float* Pc = (float*)workspace;
-  float* Pf = Pc + G_END;
+                          size_t ofs_c, size_t ofs_f, hipStream_t s, FieldK& f) {
+  float *Pc = ws_at<float>(workspace, ofs_c), *Pf = ws_at<float>(workspace, ofs_f);
   if (int32_t st = weights_packed ? 0 : mlp_pack2_launch(&coarse, Pc, &fine, Pf, s)) return st;
   f = FieldK{make_grid_args(cfg->grid), cfg->white_bkgd, cfg->lindisp, t_vals, u, table, Pc, Pf};
   return HN_OK;
@@ -365,14 +415,23 @@ static int device_cus() {
 static int fwd_pick_form(int64_t n_rays, int cus) {
   return cus > 0 && (n_rays + kFwdResWaves - 1) / kFwdResWaves >= cus ? 2 : 1;
 }
-template <bool kLoss, int kNiT>
-static void launch_fwd(bool res, int64_t n_rays, hipStream_t s, const RenderK& k) {
+// f(std::true_type or std::false_type) for a run-time b: one nesting level per
+// boolean template parameter of a kernel, however many there are
+template <class F>
+static void with_bool(bool b, F&& f) { b ? f(std::true_type{}) : f(std::false_type{}); }
+// render_fwd_kernel<kLoss, kNiT, kRes> of a call: the one place that picks the instantiation
+static void launch_fwd(bool loss, bool ni64, bool res, int64_t n_rays, hipStream_t s, const RenderK& k) {
   const int bw = fwd_block_waves(res);
   const dim3 grid((unsigned)((n_rays + bw - 1) / bw)), block(64 * bw);
-  if (res)
-    hipLaunchKernelGGL((render_fwd_kernel<kLoss, kNiT, true>), grid, block, 0, s, k);
-  else
-    hipLaunchKernelGGL((render_fwd_kernel<kLoss, kNiT, false>), grid, block, 0, s, k);
+  with_bool(loss, [&](auto kLoss) {
+    with_bool(ni64, [&](auto kNi64T) {
+      with_bool(res, [&](auto kRes) {
+        constexpr int ni = decltype(kNi64T)::value ? kNi64 : kNi;
+        hipLaunchKernelGGL((render_fwd_kernel<decltype(kLoss)::value, ni, decltype(kRes)::value>), grid, block, 0, s,
+                           k);
+      });
+    });
+  });
 }
 
 extern "C" int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus) {
@@ -414,8 +473,10 @@ extern "C" int32_t hn_render_fwd_form(const hn_render_cfg* cfg, const hn_render_
     if (plan.mode != kModeSplit) return HN_E_SHAPE;   // only the binned backward can skip its pre-pass
   }
   hipStream_t s = (hipStream_t)stream;
-  RenderK k;
-  if ((st = field_args(cfg, a->t_vals, a->u, a->table, a->coarse, a->fine, a->weights_packed, workspace, s, k.f)))
+  RenderK k{};   // (no loss: no target, d raw, marks or stamp)
+  const WsLayout& L = plan.ws;
+  if ((st = field_args(cfg, a->t_vals, a->u, a->table, a->coarse, a->fine, a->weights_packed, workspace, L.Pc, L.Pf,
+                       s, k.f)))
     return st;
   k.perturb = cfg->perturb;
   k.B = a->n_rays;
@@ -432,38 +493,36 @@ extern "C" int32_t hn_render_fwd_form(const hn_render_cfg* cfg, const hn_render_
   // 633 -> 682 us)
   k.feat_nt = cfg->grid.log2_hashmap_size > 20;
   k.skip_dead = a->skip_dead_color != 0;
-  k.ltarget = nullptr;
-  k.lgm = k.lsparse = 0.f;
-  k.draw = nullptr;
-  k.uflags = nullptr;
-  k.stamp = nullptr;
   const bool res = (form ? form : fwd_pick_form(a->n_rays, device_cus())) == 2;
   if (a->loss) {
-    const WsDraw w = ws_draw(workspace, a->n_rays);
     k.ltarget = a->loss->target;
-    k.lgm = (1.f / a->loss->world) / (float)(3 * a->n_rays);   // hn_render_bwd's factors (g_loss = 1)
-    k.lsparse = 1.f * a->loss->sparse_w;
-    k.draw = w.draw;
-    k.uflags = w.uflags;
-    k.stamp = ws_stamp(w.lmeta);
-    if (ni64)
-      launch_fwd<true, kNi64>(res, a->n_rays, s, k);
-    else
-      launch_fwd<true, kNi>(res, a->n_rays, s, k);
-  } else if (ni64) {
-    launch_fwd<false, kNi64>(res, a->n_rays, s, k);
-  } else {
-    launch_fwd<false, kNi>(res, a->n_rays, s, k);
+    loss_factors(a->loss->world, a->loss->sparse_w, a->n_rays, k.lgm, k.lsparse);
+    k.draw = ws_at<float>(workspace, L.draw);
+    k.uflags = ws_at<uint8_t>(workspace, L.marks);
+    k.stamp = ws_stamp(ws_at<int32_t>(workspace, L.lmeta));
   }
+  launch_fwd(a->loss != nullptr, ni64, res, a->n_rays, s, k);
   return hip_status(hipGetLastError());
 }
 
-// Workspace of hn_render_image: both nets' packed weights | one slot per wave of
-// the persistent grid (its current ray's two coarse feature tiles)
-static size_t image_ws_floats() { return (size_t)2 * G_END + (size_t)kImgBlocks * kImgBlockWaves * kImgSlotFloats; }
+// Workspace of hn_render_image (offsets in floats): both nets' packed weights |
+// one slot per wave of the persistent grid (its current ray's two coarse
+// feature tiles, ImageK::slots)
+struct ImageWs {
+  size_t Pc, Pf, slots, total;
+};
+static ImageWs image_ws_layout() {
+  WsCursor c;
+  ImageWs w;
+  w.Pc = c.take(G_END);
+  w.Pf = c.take(G_END);
+  w.slots = c.take((size_t)kImgBlocks * kImgBlockWaves * kImgSlotFloats);
+  w.total = c.at;
+  return w;
+}
 
 extern "C" size_t hn_render_image_workspace_bytes(const hn_render_cfg* cfg) {
-  return check_image_cfg(cfg) ? 0 : image_ws_floats() * sizeof(float);
+  return check_image_cfg(cfg) ? 0 : image_ws_layout().total * sizeof(float);
 }
 
 extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
@@ -478,7 +537,8 @@ extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_im
   if (!a->poses || !a->t_vals || !a->u || !a->table || !mlp_ok(a->coarse) || !mlp_ok(a->fine)) return HN_E_NULL;
   if (!a->rgb || !a->depth || !a->acc) return HN_E_NULL;
   if (!workspace) return HN_E_NULL;
-  if (ws_bytes < image_ws_floats() * sizeof(float)) return HN_E_WORKSPACE;
+  const ImageWs L = image_ws_layout();
+  if (ws_bytes < L.total * sizeof(float)) return HN_E_WORKSPACE;
   ImageK k;
   k.Hb = ((uint32_t)a->H + 1) / 2;
   k.Wb = ((uint32_t)a->W + 1) / 2;
@@ -488,14 +548,15 @@ extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_im
                                                    : (uint64_t)a->n_views * k.Hb * k.Wb;
   if (groups > 0x7fffffffull) return HN_E_SHAPE;
   hipStream_t s = (hipStream_t)stream;
-  if ((st = field_args(cfg, a->t_vals, a->u, a->table, a->coarse, a->fine, a->weights_packed, workspace, s, k.f)))
+  if ((st = field_args(cfg, a->t_vals, a->u, a->table, a->coarse, a->fine, a->weights_packed, workspace, L.Pc, L.Pf,
+                       s, k.f)))
     return st;
   k.variant = variant;
   k.n_views = a->n_views; k.H = a->H; k.W = a->W; k.pose_stride = a->pose_stride;
   k.groups = (uint32_t)groups;
   k.fx = a->fx; k.fy = a->fy; k.cx = a->cx; k.cy = a->cy; k.near = a->near; k.far = a->far;
   k.poses = a->poses;
-  k.slots = (variant & kImgReencode) ? nullptr : (float*)workspace + 2 * (size_t)G_END;
+  k.slots = (variant & kImgReencode) ? nullptr : ws_at<float>(workspace, L.slots);
   k.rgb = a->rgb; k.depth = a->depth; k.acc = a->acc; k.rays = a->rays;
   hipLaunchKernelGGL(render_image_kernel, dim3(kImgBlocks), dim3(64 * kImgBlockWaves), 0, s, k);
   return hip_status(hipGetLastError());
@@ -528,8 +589,8 @@ extern "C" int32_t hn_render_bwd_owner(const hn_render_cfg* cfg, const hn_render
   if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
   if (bin_lo < 0 || bin_hi > plan.bg.nbins || bin_lo > bin_hi) return HN_E_SHAPE;
   if (bin_lo == bin_hi) return HN_OK;
-  launch_owner(owner_args(cfg, a, (float*)workspace + plan.bins, plan.bg, bin_lo), plan.bg, bin_hi - bin_lo,
-               (hipStream_t)stream);
+  launch_owner(owner_args(cfg, a, ws_at<float>(workspace, plan.ws.bins), plan.bg, bin_lo), plan.bg,
+               bin_hi - bin_lo, (hipStream_t)stream);
   return hip_status(hipGetLastError());
 }
 
@@ -541,7 +602,6 @@ extern "C" int32_t hn_render_bwd_owner(const hn_render_cfg* cfg, const hn_render
 // bitwise reproducible where hn_tv_bwd's float atomics are not.
 static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* workspace,
                            size_t ws_bytes, hipStream_t s) {
-  const int T = cfg->grid.log2_hashmap_size;
   if (!a->g_tv || (!a->d_table && !a->table_step) || !workspace) return HN_E_NULL;
   if (a->d_table_mode < 0 || a->d_table_mode > 3 || a->owner_defer || a->mlp_step || a->repack || a->loss)
     return HN_E_SHAPE;
@@ -550,19 +610,16 @@ static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a
   int32_t st = check_table_step(cfg, a);
   if (st) return st;
   TvK tvk;
-  int nbf, nbb;
-  if ((st = make_tv(a->tv, tvk, nbf, nbb))) return st;
-  if (a->tv->n_levels != cfg->grid.n_levels || a->tv->log2_hashmap_size != T) return HN_E_SHAPE;
-  for (int l = 0; l < a->tv->n_levels; ++l)
-    if (a->tv->cube[l] > kTvRecMaxCube) return HN_E_SHAPE;
+  bool rec_fit;
+  if ((st = check_tv(cfg, a, tvk, rec_fit))) return st;
+  if (!rec_fit) return HN_E_SHAPE;
   if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
   if (!sc_lds_fits(plan)) return HN_E_SHAPE;
   const BinGeom& bg = plan.bg;
-  float* bins = (float*)workspace + plan.bins;
+  float* bins = ws_at<float>(workspace, plan.ws.bins);
   // the overflow book starts empty (render_comp_bwd_kernel's zero_ovf_book
   // on a rendering rank): total, per-bin spills, placement cursors
-  const size_t nrec = bin_records(bg.nbins, bg.cap, 0);
-  const OvfBook ob = ovf_book(reinterpret_cast<uint32_t*>(bins + 4 * nrec), nrec, bg.nbins);
+  const OvfBook ob = host_ovf_book(bins, bg, 0);
   if ((st = hip_status(hipMemsetAsync(ob.cnt, 0, (1 + 2 * (size_t)bg.nbins) * sizeof(uint32_t), s)))) return st;
   ScK sk{};
   sk.g = make_grid_args(cfg->grid);
@@ -572,14 +629,19 @@ static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a
   sk.slab = nullptr;   // no MLP gradients: the caller's stay untouched
   hipLaunchKernelGGL(scatter_bins_kernel, dim3(kBwdBlocks), dim3(64 * kScWaves), plan.sc_lds, s, sk);
   if ((st = hip_status(hipGetLastError()))) return st;
-  hn_render_bwd_args b = *a;
-  b.n_rays = 0;
-  const BinR r = owner_args(cfg, &b, bins, bg, 0);
+  const BinR r = owner_args(cfg, a, bins, bg, 0);   // (a->n_rays is 0 here)
   hipLaunchKernelGGL(ovf_place_kernel, dim3(kBwdBlocks), dim3(kPlaceThreads), 0, s, r, PackK{}, MortonK{},
                      (unsigned)kBwdBlocks);
   if ((st = hip_status(hipGetLastError()))) return st;
   launch_owner(r, bg, bg.nbins, s);
   return hip_status(hipGetLastError());
+}
+
+// The composite pre-pass of either schedule: a wave per (ray, pass), and a
+// workgroup ahead of them for the loss value where the call forms one
+static void launch_prepass(const B1K& k, hipStream_t s) {
+  hipLaunchKernelGGL(render_comp_bwd_kernel, dim3((unsigned)((2 * k.B + kFwdWaves - 1) / kFwdWaves + (k.lout ? 1 : 0))),
+                     dim3(64 * kFwdWaves), 0, s, k);
 }
 
 // The binned schedule (hn_bwd_binned.h): pre-pass, lists, MLP backward,
@@ -594,10 +656,7 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
   // kernel checks its stamp and takes the pre-pass's side jobs in one extra
   // workgroup (dense_bwd = 1 runs the same kernel, listing every group)
   const int prepass = a->prepass_done ? 1 : 0;
-  if (!prepass)
-    hipLaunchKernelGGL(render_comp_bwd_kernel,
-                       dim3((unsigned)((2 * a->n_rays + kFwdWaves - 1) / kFwdWaves + (k.lout ? 1 : 0))),
-                       dim3(64 * kFwdWaves), 0, s, k);
+  if (!prepass) launch_prepass(k, s);
   // the backward's work lists (from the marks)
   const int64_t nlb = (a->n_rays + kListThreads - 1) / kListThreads;
   // (+ the next batch's tile counts and uniform draws, dispatched behind them)
@@ -616,8 +675,7 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
   sk.scramble = k.scramble;
   sk.skip_zero = k.skip_zero;
   sk.lmeta = k.lmeta;
-  // the scatter's group list
-  sk.slist = k.skip_zero ? k.lists + 16 * a->n_rays : nullptr;
+  sk.slist = k.skip_zero ? ws_at<int32_t>(workspace, plan.ws.ls) : nullptr;   // the scatter's group list
   sk.z_fine = a->z_fine;
   sk.fine_src = a->fine_src;
   sk.dfeat_f = k.dfeat_f;
@@ -641,7 +699,7 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
   if (a->repack) {   // validated: mlp_step given
     pk.c = a->coarse;
     pk.f = a->fine;
-    pk.P = (float*)workspace;
+    pk.P = ws_at<float>(workspace, plan.ws.Pc);   // [2][G_END]: Pc, then Pf
     pblocks = (unsigned)((2 * G_END + kPlaceThreads - 1) / kPlaceThreads);
   }
   // (+ the next batch's rays: every tile's count is in place since the lists launch)
@@ -666,9 +724,7 @@ static int32_t bwd_atomic(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
     const size_t tb = ((size_t)16 << T) * 2 * sizeof(float);
     if ((st = hip_status(hipMemsetAsync(a->d_table, 0, tb, s)))) return st;
   }
-  hipLaunchKernelGGL(render_comp_bwd_kernel,
-                     dim3((unsigned)((2 * a->n_rays + kFwdWaves - 1) / kFwdWaves + (k.lout ? 1 : 0))),
-                     dim3(64 * kFwdWaves), 0, s, k);
+  launch_prepass(k, s);
   const size_t lds = (size_t)kB1LdsF * sizeof(float);
   // 16 levels x 2^T x 8 B >= 256 MiB from T = 21: the table no longer fits the MALL
   if (T >= 21)
@@ -683,43 +739,44 @@ static int32_t bwd_atomic(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
   return hip_status(hipGetLastError());
 }
 
-extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
-                                 void* workspace, size_t ws_bytes, void* stream) {
-  // ---- validation ----
+// What hn_render_bwd's checks settle for its launches
+struct BwdCall {
+  BwdPlan plan;
+  TvK tvk;
+  // TV term: records of the binned scatter (tv_rec), or hn_tv_bwd into d_table (tv_atomic)
+  const hn_tv_args *tv_rec = nullptr, *tv_atomic = nullptr;
+  NextK nk{};   // the next batch's job (none: no workgroups)
+};
+
+// Every check of hn_render_bwd: host work only, so a refused call queues
+// nothing.  (A call with no rays is left to tv_only_bwd's checks.)
+static int32_t check_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* workspace, size_t ws_bytes,
+                         BwdCall& c) {
   int32_t st = check_cfg(cfg);
   if (st) return st;
   if (!a) return HN_E_NULL;
   if (a->n_rays < 0) return HN_E_SHAPE;
   // the next batch rides the lists and placement launches of a backward that runs both
   if (a->next_batch && (a->n_rays == 0 || a->owner_defer)) return HN_E_SHAPE;
-  if (a->n_rays == 0) return a->tv ? tv_only_bwd(cfg, a, workspace, ws_bytes, (hipStream_t)stream) : HN_OK;
+  if (a->n_rays == 0) return HN_OK;
   if (!a->rays || !a->table || !mlp_ok(a->coarse) || !mlp_ok(a->fine)) return HN_E_NULL;
   if (!a->z_coarse || !a->z_fine || !a->raw_c || !a->raw_f || !a->fine_src || !a->feat)
     return HN_E_NULL;
   if ((!a->d_table && !a->table_step) || !grad_ok(a->d_coarse) || !grad_ok(a->d_fine)) return HN_E_NULL;
   if (a->d_table_mode < 0 || a->d_table_mode > 3) return HN_E_SHAPE;
   if (!workspace) return HN_E_NULL;
-  const BwdPlan plan = bwd_plan(cfg, a->n_rays);
-  const bool binned = plan.mode == kModeSplit;
-  if (ws_bytes < plan.bytes()) return HN_E_WORKSPACE;
+  c.plan = bwd_plan(cfg, a->n_rays);
+  const bool binned = c.plan.mode == kModeSplit;
+  if (ws_bytes < c.plan.bytes()) return HN_E_WORKSPACE;
   if (cfg->n_importance == kNi64 && !binned) return HN_E_SHAPE;   // the float-atomic schedule is 64 + 128 only
-  // the next batch's job: hn_sample_batch_morton's checks and codes, before anything is queued
-  NextK nk{};
-  if (a->next_batch) {
+  if (a->next_batch) {   // hn_sample_batch_morton's checks and codes
     if (!binned) return HN_E_SHAPE;
     const hn_next_batch& nb = *a->next_batch;
-    if ((st = make_uni(nb.seed, nb.draws, nb.n_draws, nk.u))) return st;
+    if ((st = make_uni(nb.seed, nb.draws, nb.n_draws, c.nk.u))) return st;
     if ((st = make_morton(nb.sampler, nb.image, nb.c2w, nb.n_rays, nb.rays, nb.target, nb.workspace, nb.ws_bytes,
-                          nk.m)))
+                          c.nk.m)))
       return st;
   }
-  // the weights' packed copies: the one launch ahead of the remaining checks
-  // (its status, where it fails, decides before theirs)
-  hipStream_t s = (hipStream_t)stream;
-  float* Pc = (float*)workspace;
-  float* Pf = Pc + G_END;
-  if (!a->weights_packed && (st = mlp_pack2_launch(&a->coarse, Pc, &a->fine, Pf, s))) return st;
-  const int T = cfg->grid.log2_hashmap_size;
   if (a->loss) {   // ABI 13: the training loss formed by the pre-pass (hn_render_loss)
     const hn_render_loss& L = *a->loss;
     if (!L.target || !L.rgb || !L.rgb0 || !L.sparsity || !L.sparsity0 || !L.out || (L.n_tv && !L.tv))
@@ -732,21 +789,14 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   // the fused table step lives in the binned scatter's owner pass
   if (a->table_step && !binned) return HN_E_SHAPE;
   if ((st = check_table_step(cfg, a))) return st;
-  // TV term: records of the binned scatter (tv_rec), or hn_tv_bwd into d_table (tv_atomic)
-  TvK tvk;
-  const hn_tv_args *tv_rec = nullptr, *tv_atomic = nullptr;
   if (a->tv) {
-    if (!a->g_tv) return HN_E_NULL;
-    int nbf, nbb;
-    if ((st = make_tv(a->tv, tvk, nbf, nbb))) return st;
-    if (a->tv->n_levels != cfg->grid.n_levels || a->tv->log2_hashmap_size != T) return HN_E_SHAPE;
-    bool small = a->tv->n_levels <= 16;
-    for (int l = 0; l < a->tv->n_levels && small; ++l) small = a->tv->cube[l] <= kTvRecMaxCube;
-    if (binned && small) {   // the overflow lists hold these records (ovf_per_block)
-      tv_rec = a->tv;
+    bool rec_fit;
+    if ((st = check_tv(cfg, a, c.tvk, rec_fit))) return st;
+    if (binned && rec_fit) {
+      c.tv_rec = a->tv;
     } else {
       if (a->table_step || !a->d_table) return HN_E_SHAPE;
-      tv_atomic = a->tv;
+      c.tv_atomic = a->tv;
     }
   }
   if (a->owner_defer && !binned) return HN_E_SHAPE;
@@ -760,62 +810,74 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
       if (r.n != numel[t % 5]) return HN_E_SHAPE;
     }
   }
-  if (binned && !sc_lds_fits(plan)) return HN_E_SHAPE;   // bins beyond the LDS counters' room
+  if (binned && !sc_lds_fits(c.plan)) return HN_E_SHAPE;   // bins beyond the LDS counters' room
+  return HN_OK;
+}
 
-  // ---- the MLP backward's arguments ----
-  B1K k;
+// The MLP backward's arguments of a checked call
+static B1K fill_b1k(const hn_render_cfg* cfg, const hn_render_bwd_args* a, const BwdPlan& plan, void* workspace) {
+  const WsLayout& L = plan.ws;
+  const bool binned = plan.mode == kModeSplit;
+  B1K k{};   // (no loss: none of its inputs, factors 0)
   k.B = a->n_rays;
-  k.scramble = 0;
-  if (a->n_rays > 1) {
+  if (a->n_rays > 1) {   // else scramble 0
     int bits = 2;
     while ((1ll << bits) < a->n_rays) bits += 2;
     k.scramble = bits / 2;
   }
   k.white = cfg->white_bkgd;
   k.rays = a->rays; k.noise_c = a->noise_c; k.noise_f = a->noise_f;
-  k.Pc = Pc; k.Pf = Pf;
+  k.Pc = ws_at<float>(workspace, L.Pc); k.Pf = ws_at<float>(workspace, L.Pf);
   k.z_coarse = a->z_coarse; k.z_fine = a->z_fine; k.raw_c = a->raw_c; k.raw_f = a->raw_f;
   k.feat = a->feat;
   k.g_rgb = a->g_rgb; k.g_depth = a->g_depth; k.g_acc = a->g_acc; k.g_sparsity = a->g_sparsity;
   k.g_rgb0 = a->g_rgb0; k.g_depth0 = a->g_depth0; k.g_acc0 = a->g_acc0;
   k.g_sparsity0 = a->g_sparsity0; k.g_raw_f = a->g_raw_f;
-  const WsDraw w = ws_draw(workspace, a->n_rays);
-  k.slab = w.slab;
-  k.dfeat = w.dfeat;
-  k.draw = w.draw;
-  k.uflags = w.uflags;
-  k.lmeta = w.lmeta;
-  k.lists = k.lmeta + 8;
-  k.ltarget = k.lrgb = k.lrgb0 = k.lsp = k.lsp0 = k.ltv = nullptr;
-  k.n_tv = 0;
-  k.lgm = k.lsparse = k.lworld = k.lsparse_w = k.ltv_w = 0.f;
-  k.lout = nullptr;
+  k.slab = ws_at<float>(workspace, L.slab);
+  k.dfeat = ws_at<float>(workspace, L.dfeat);
+  k.draw = ws_at<float>(workspace, L.draw);
+  k.uflags = ws_at<uint8_t>(workspace, L.marks);
+  k.lmeta = ws_at<int32_t>(workspace, L.lmeta);
+  k.lists = ws_at<int32_t>(workspace, L.lc);   // (the kernels find the fine list behind the coarse one)
   k.skip_zero = cfg->dense_bwd ? 0 : 1;
   k.sf = kSc + cfg->n_importance;
   if (a->loss) {
-    const hn_render_loss& L = *a->loss;
-    const float g = 1.f;   // hn_loss_bwd's factors with g_loss = 1
-    k.lgm = (g / L.world) / (float)(3 * a->n_rays);
-    k.lsparse = g * L.sparse_w;
-    k.ltarget = L.target; k.lrgb = L.rgb; k.lrgb0 = L.rgb0; k.lsp = L.sparsity; k.lsp0 = L.sparsity0;
-    k.ltv = L.n_tv ? L.tv : nullptr;
-    k.n_tv = L.n_tv;
-    k.lworld = L.world; k.lsparse_w = L.sparse_w; k.ltv_w = L.tv_w;
-    k.lout = L.out;
+    const hn_render_loss& l = *a->loss;
+    loss_factors(l.world, l.sparse_w, a->n_rays, k.lgm, k.lsparse);
+    k.ltarget = l.target; k.lrgb = l.rgb; k.lrgb0 = l.rgb0; k.lsp = l.sparsity; k.lsp0 = l.sparsity0;
+    k.ltv = l.n_tv ? l.tv : nullptr;
+    k.n_tv = l.n_tv;
+    k.lworld = l.world; k.lsparse_w = l.sparse_w; k.ltv_w = l.tv_w;
+    k.lout = l.out;
   }
   k.g = make_grid_args(cfg->grid);
   k.fine_src = a->fine_src;
   k.d_table = a->d_table;
-  k.bins = binned ? (float*)workspace + plan.bins : nullptr;
+  k.bins = binned ? ws_at<float>(workspace, L.bins) : nullptr;
   k.bin_cap = plan.bg.cap;
   k.bin_shift = plan.bg.shift;
   k.nbins = plan.bg.nbins;
-  k.dfeat_f = binned ? (float*)workspace + plan.dfeat_f : nullptr;
+  k.dfeat_f = binned ? ws_at<float>(workspace, L.dfeat_f) : nullptr;
+  return k;
+}
 
-  // ---- one schedule; then, under either, a TV term that is not in the
-  // records: hn_tv_bwd's atomics into d_table ----
-  if ((st = binned ? bwd_binned(cfg, a, plan, k, tv_rec, tvk, nk, workspace, s) : bwd_atomic(cfg, a, k, s)))
+extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
+                                 void* workspace, size_t ws_bytes, void* stream) {
+  BwdCall c;
+  int32_t st = check_bwd(cfg, a, workspace, ws_bytes, c);
+  if (st) return st;
+  hipStream_t s = (hipStream_t)stream;
+  if (a->n_rays == 0) return a->tv ? tv_only_bwd(cfg, a, workspace, ws_bytes, s) : HN_OK;
+  const B1K k = fill_b1k(cfg, a, c.plan, workspace);
+  // the weights' packed copies, then one schedule; then, under either, a TV
+  // term that is not in the records: hn_tv_bwd's atomics into d_table
+  const WsLayout& L = c.plan.ws;
+  if (!a->weights_packed && (st = mlp_pack2_launch(&a->coarse, ws_at<float>(workspace, L.Pc), &a->fine,
+                                                   ws_at<float>(workspace, L.Pf), s)))
     return st;
-  if (tv_atomic) return hn_tv_bwd(tv_atomic, a->g_tv, a->d_table, stream);
+  if ((st = c.plan.mode == kModeSplit ? bwd_binned(cfg, a, c.plan, k, c.tv_rec, c.tvk, c.nk, workspace, s)
+                                      : bwd_atomic(cfg, a, k, s)))
+    return st;
+  if (c.tv_atomic) return hn_tv_bwd(c.tv_atomic, a->g_tv, a->d_table, stream);
   return HN_OK;
 }

@@ -445,12 +445,7 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     if table_step is not None:
         p, m, v, c = table_step
         L.require_device(p, m, v)
-        step = L.HnRadamTensor()
-        step.p, step.g, step.m, step.v = p.data_ptr(), None, m.data_ptr(), v.data_ptr()
-        step.n = p.numel()
-        for k in ("beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps", "neg_wd_lr", "neg_step_lr",
-                  "mode", "has_wd"):
-            setattr(step, k, c[k])
+        step = _radam_fill(L.HnRadamTensor(), p, None, m, v, c)
         a.table_step = C.pointer(step)
         if table_live is not None:
             n_lv, words = table_live
@@ -478,10 +473,7 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
             if p.data_ptr() != w.data_ptr():
                 raise ValueError("hashnerf_amd.render_bwd: mlp_step must follow the render's weights in order")
             L.require_device(p, m, v)
-            d.p, d.g, d.m, d.v, d.n = p.data_ptr(), None, m.data_ptr(), v.data_ptr(), p.numel()
-            for k in ("beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps", "neg_wd_lr", "neg_step_lr",
-                      "mode", "has_wd"):
-                setattr(d, k, c[k])
+            _radam_fill(d, p, None, m, v, c)
         a.mlp_step = ms
         a.repack = 1 if repack else 0
         keep.append(ms)
@@ -633,9 +625,11 @@ def torch_uniform(shapes, dev):
     return outs
 
 
-def _ray_sampler(image, c2w, K, near, far, crop, seed):
-    """hn_ray_sampler of one image and window, and the contiguous image and
-    [3, 4] pose it is used with."""
+def _ray_sampler(who, image, c2w, n_rays, K, near, far, crop, seed, morton=True):
+    """What sample_rays and next_batch set up alike: the hn_ray_sampler of one
+    image and window, the contiguous image and [3, 4] pose it is used with,
+    the [n, 11] rays and [n, 3] target to fill and, for the Morton order, the
+    sampler's scratch and its size (None, 0 without)."""
     L.require_device(image, c2w)
     image, c2w = image.contiguous(), c2w[:3, :4].contiguous()
     s = L.HnRaySampler()
@@ -644,7 +638,13 @@ def _ray_sampler(image, c2w, K, near, far, crop, seed):
     s.fx, s.fy, s.cx, s.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
     s.near, s.far = float(near), float(far)
     s.seed = int(seed) & ((1 << 64) - 1)
-    return s, image, c2w
+    nb = L.lib().hn_sample_rays_morton_workspace_bytes(s) if morton else 0
+    if morton and nb == 0:
+        raise ValueError(f"{who}: window {s.crop_h}x{s.crop_w} too large")
+    dev = image.device
+    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
+    target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+    return s, image, c2w, rays, target, _sampler_ws(dev, nb) if morton else None, nb
 
 
 class NextBatch:
@@ -661,14 +661,8 @@ def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None):
     launches.  render_bwd(next_batch=...) of the binned schedule runs the
     device half inside its own two small launches, bitwise the values
     sample_rays would return."""
-    s, image, c2w = _ray_sampler(image, c2w, K, near, far, crop, seed)
+    s, image, c2w, rays, target, ws, nb = _ray_sampler("next_batch", image, c2w, n_rays, K, near, far, crop, seed)
     dev = image.device
-    nb = L.lib().hn_sample_rays_morton_workspace_bytes(s)
-    if nb == 0:
-        raise ValueError(f"next_batch: window {s.crop_h}x{s.crop_w} too large")
-    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
-    target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
-    ws = _sampler_ws(dev, nb)
     useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
     j = L.HnNextBatch()
     j.sampler = C.pointer(s)
@@ -695,15 +689,10 @@ def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=
     order.  Both are deterministic for a given seed.  uniforms: shapes of
     torch.rand draws to make as well (torch_uniform; with order=1 in the
     sampler's first launch), returned after rays and target."""
-    s, image, c2w = _ray_sampler(image, c2w, K, near, far, crop, seed)
+    s, image, c2w, rays, target, ws, nb = _ray_sampler("sample_rays(order=1)", image, c2w, n_rays, K, near, far,
+                                                       crop, seed, morton=order == 1)
     dev = image.device
-    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
-    target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
     if order == 1:
-        nb = L.lib().hn_sample_rays_morton_workspace_bytes(s)
-        if nb == 0:
-            raise ValueError(f"sample_rays(order=1): window {s.crop_h}x{s.crop_w} too large")
-        ws = _sampler_ws(dev, nb)
         if uniforms:
             useed, arr, outs = _uniform_draws(uniforms, dev)
             L.check(L.lib().hn_sample_batch_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
@@ -970,6 +959,17 @@ class TVFn(torch.autograd.Function):
         return dtable, None, None, None
 
 
+def _radam_fill(d, p, g, m, v, c):
+    """One HnRadamTensor: the tensors' pointers (g None: a fused step, which
+    forms the gradient itself) and the nine coefficients of dict c."""
+    d.p, d.g, d.m, d.v = p.data_ptr(), None if g is None else g.data_ptr(), m.data_ptr(), v.data_ptr()
+    d.n = p.numel()
+    for k in ("beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps", "neg_wd_lr", "neg_step_lr",
+              "mode", "has_wd"):
+        setattr(d, k, c[k])
+    return d
+
+
 def _radam_array(tensors, name):
     arr = (L.HnRadamTensor * len(tensors))()
     for d, (p, g, m, v, c) in zip(arr, tensors):
@@ -977,11 +977,7 @@ def _radam_array(tensors, name):
         for t in (p, g, m, v):
             if not t.is_contiguous():
                 raise RuntimeError(f"hashnerf_amd.{name}: tensors must be contiguous")
-        d.p, d.g, d.m, d.v = p.data_ptr(), g.data_ptr(), m.data_ptr(), v.data_ptr()
-        d.n = p.numel()
-        for k in ("beta1", "beta2", "one_minus_beta1", "one_minus_beta2", "eps", "neg_wd_lr",
-                  "neg_step_lr", "mode", "has_wd"):
-            setattr(d, k, c[k])
+        _radam_fill(d, p, g, m, v, c)
     return arr
 
 
