@@ -198,7 +198,8 @@ def test_dp_two_ranks_equal_global_batch(hn, tmp_path, B, T, HW, i):
 def test_trainer_one_rank_gradient_vs_oracle(hn, oracle):
     """The explicit trainer's launch sequence (sampler batch, fused render,
     TV, fused loss, binned backward + TV backward) on 32 rays against the
-    oracle's autograd of run_nerf.py:612-636 with the same inputs."""
+    oracle's autograd of run_nerf.py:612-636 with the same inputs.
+    (The samples' own check leaves 3 % of the fine z out; test_gpu_sampling.py judges every importance sample.)"""
     from hashnerf_pytorch_amd import functional as HF
     O = oracle
     tr, _ = _trainer(hn, 32)

@@ -228,7 +228,8 @@ def test_forward_deterministic_config3_shape(hn):
 def test_binned_vs_oracle_bench_shape(hn, oracle):
     """T=19, finest 512, 4096 rays (BASELINE configs[1] shape): the binned
     table and MLP gradients against the oracle on a 32-ray subset of the
-    loss (rays are independent, so the subset's gradient is exact)."""
+    loss (rays are independent, so the subset's gradient is exact).
+    (The samples' own check leaves 3 % of the fine z out; test_gpu_sampling.py judges every importance sample.)"""
     O = oracle
     HF, emb, mc, mf, ws, rays, t_rand, u, target, st, _ = _state(hn, 4096, 19, 11, "binned")
     n = 32
