@@ -21,43 +21,26 @@ import numpy as np
 import pytest
 import torch
 
+from gpu_support import BLENDER_BOX, MLP_KW, blender_nets, close, hf, rel_close
+
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 T = 14
-BOX = (torch.tensor([-4.0, -4.0, -3.4]), torch.tensor([4.0, 4.0, 3.3]))
-
-
-def _close(a, b, rtol, atol, msg):
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def _rel(a, b, tol, msg):
-    a = a.detach().cpu().numpy().astype(np.float64)
-    b = b.detach().cpu().numpy().astype(np.float64)
-    err = np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
-    assert err <= tol, f"{msg}: relative error {err:.3e}"
+BOX = BLENDER_BOX
 
 
 def _setup(hn, B, seed):
-    torch.manual_seed(seed)
-    emb = hn.HashEmbedder(BOX, log2_hashmap_size=T, finest_resolution=512).to(DEV)
-    with torch.no_grad():
-        emb.table.uniform_(-0.5, 0.5)
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    mc, mf = hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)
+    n = blender_nets(hn, T, seed)
     focal, K = hn.rays.blender_intrinsics(100, 100)
     c2w = hn.pose_spherical(40.0 + seed, -30.0, 4.0)
     ro, rd = hn.get_rays(100, 100, K, c2w[:3, :4].to(DEV))
     sel = torch.randperm(100 * 100, device=DEV)[:B]
     rays = torch.stack([ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]], 0)
-    return emb, mc, mf, K, rays
+    return n.emb, n.mc, n.mf, K, rays
 
 
 def _render(hn, emb, mc, mf, K, rays):
-    from importlib import import_module
-    HF = import_module("hashnerf_pytorch_amd.functional")
+    HF = hf()
     nq = hn.NetworkQuery(emb, hn.SHEncoder())
     HF.DEBUG_KEEP = True
     try:
@@ -95,14 +78,14 @@ def test_fused_step_ragged_batches(hn, oracle, B):
     assert same.mean() > 0.97, f"only {same.mean():.4f} of fine samples agree"
     for k, a in (("rgb_map", rgb), ("depth_map", depth), ("acc_map", acc), ("rgb0", ex["rgb0"]),
                  ("sparsity_loss", ex["sparsity_loss"]), ("sparsity_loss0", ex["sparsity_loss0"])):
-        _close(a, ret[k].detach().numpy(), rtol=1e-4, atol=2e-5, msg=f"B={B} {k}")
+        close(a, ret[k].detach().numpy(), rtol=1e-4, atol=2e-5, msg=f"B={B} {k}")
     ref_loss = O.training_loss(ret, target.cpu(), 1e-3)
-    _close(loss.item(), ref_loss.item(), rtol=1e-5, atol=1e-7, msg=f"B={B} loss")
+    close(loss.item(), ref_loss.item(), rtol=1e-5, atol=1e-7, msg=f"B={B} loss")
     ref_loss.backward()
-    _rel(emb.table.grad, tab.grad, 5e-4, f"B={B} table grad")
+    rel_close(emb.table.grad, tab.grad, 5e-4, f"B={B} table grad")
     for w_dev, w_ref in ((mc.weights(), wc), (mf.weights(), wf)):
         for p, k in zip(w_dev, O.MLP_KEYS):
-            _rel(p.grad, w_ref[k].grad, 5e-4, f"B={B} {k}")
+            rel_close(p.grad, w_ref[k].grad, 5e-4, f"B={B} {k}")
 
 
 def test_empty_batch(hn):
@@ -139,15 +122,12 @@ def test_config3_full_size_ray_subset(hn, oracle):
     emb = hn.HashEmbedder(BOX, log2_hashmap_size=Tb, finest_resolution=finest).to(DEV)
     with torch.no_grad():
         emb.table.uniform_(-0.5, 0.5)
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    mc, mf = hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)
+    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
     focal, K = hn.rays.blender_intrinsics(400, 400)
     ro, rd = hn.get_rays(400, 400, K, hn.pose_spherical(-60.0, -30.0, 4.0)[:3, :4].to(DEV))
     sel = torch.randperm(400 * 400, device=DEV)[:B]
     rays = torch.stack([ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]], 0)
-    from importlib import import_module
-    HF = import_module("hashnerf_pytorch_amd.functional")
+    HF = hf()
     nq = hn.NetworkQuery(emb, hn.SHEncoder())
     HF.DEBUG_KEEP = True
     try:
@@ -178,10 +158,10 @@ def test_config3_full_size_ray_subset(hn, oracle):
     same = np.isclose(z_fine[subd].cpu().numpy(), ret["z_vals"].detach().numpy(), rtol=0, atol=1e-5)
     assert same.mean() > 0.97, f"only {same.mean():.4f} of fine samples agree"
     for k, a in (("rgb_map", rgb), ("depth_map", depth), ("acc_map", acc), ("rgb0", ex["rgb0"])):
-        _close(a[subd], ret[k].detach().numpy(), rtol=1e-4, atol=2e-5, msg=k)
+        close(a[subd], ret[k].detach().numpy(), rtol=1e-4, atol=2e-5, msg=k)
     ref = ((ret["rgb_map"] - target) ** 2).sum() + ((ret["rgb0"] - target) ** 2).sum()
     ref.backward()
-    _rel(emb.table.grad, tab.grad, 5e-4, "table grad (T=22)")
+    rel_close(emb.table.grad, tab.grad, 5e-4, "table grad (T=22)")
     for w_dev, w_ref in ((mc.weights(), wc), (mf.weights(), wf)):
         for p, k in zip(w_dev, O.MLP_KEYS):
-            _rel(p.grad, w_ref[k].grad, 5e-4, k)
+            rel_close(p.grad, w_ref[k].grad, 5e-4, k)

@@ -6,16 +6,16 @@ their order are the same, so every output is compared bitwise.
 Shapes: T=14, finest 64; B in {1, 5, 16, 17, 37, 256}: one ray (15 waves of
 the resident workgroup only copy and leave after the barrier), a partial
 workgroup, exactly one, one + one ray, two full + a partial one, 16 full."""
+from types import SimpleNamespace
+
 import pytest
 import torch
 
-from conftest import pcg_table
+from gpu_support import (MLP_KW, OUT_KEYS, SMALL_T as T, backward_after_loss_forward as backward, bits_equal,
+                         small_scene, ws_offsets, ws_stamp)
 
 DEV = torch.device("cuda:0")
-T, FINEST = 14, 64
 BS = (1, 5, 16, 17, 37, 256)
-OUT_KEYS = ("rgb", "depth", "acc", "sparsity", "rgb0", "depth0", "acc0", "sparsity0", "z_std", "z_coarse", "z_fine",
-            "raw_c", "raw_f")
 # loss mode, importance samples, skip_dead_color, perturb + raw noise, white background: every factor at both
 # levels, every pair of factors at three or four of its combinations
 VARIANTS = (
@@ -29,21 +29,10 @@ VARIANTS = (
     dict(loss=True, ni=64, skip=False, noise=True, white=True),
 )
 
-_SCENES = {}
-
-
-def bits_equal(a, b):
-    """torch.equal on the bit patterns (a NaN depth of an empty ray compares equal to itself)."""
-    if a.dtype == torch.float32:
-        a, b = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
-    return a.shape == b.shape and torch.equal(a, b)
-
 
 def make_nets(hn, seed=5):
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
     torch.manual_seed(seed)
-    nets = [hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)]   # coarse and fine: different weights
+    nets = [hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)]   # coarse and fine: different weights
     return [w.detach() for n in nets for w in n.weights()]
 
 
@@ -51,15 +40,8 @@ def scene(hn, B):
     """Rays, targets, draws (for both fine-pass shapes), table and the two nets,
     built once per B and left unchanged.  Half of the space has no density,
     so tiles with and without the colour net both occur."""
-    if B in _SCENES:
-        return _SCENES[B]
-    g = torch.Generator().manual_seed(300 + B)
-    box = (torch.tensor([-1.5, -1.5, -1.5]), torch.tensor([1.5, 1.5, 1.5]))
-    emb = hn.HashEmbedder(box, log2_hashmap_size=T, finest_resolution=FINEST).to(DEV)
-    ws = make_nets(hn)
-    assert not torch.equal(ws[0], ws[5])
-    with torch.no_grad():
-        emb.table.copy_(torch.from_numpy(pcg_table(7, T)).to(DEV))
+    def half_space_density(emb, nets, ws):
+        assert not torch.equal(ws[0], ws[5])
         # density where x < 0 only: the coarsest level's first feature is +-0.5
         # by the vertex's side (its 17^3 vertices, the few that share a row
         # taking the later one's), and both nets' raw sigma is relu of it alone
@@ -71,35 +53,25 @@ def scene(hn, B):
             s0[0, 0] = 1.0
             s1[0].zero_()
             s1[0, 0] = 1.0
-    _, K = hn.rays.blender_intrinsics(100, 100)
-    c2w = hn.pose_spherical(30.0, -30.0, 4.0)
-    ro, rd = hn.get_rays(100, 100, K, c2w[:3, :4].to(DEV))
-    sel = torch.randperm(100 * 100, generator=g)[:B].to(DEV)
-    o, d = ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]
-    rays = torch.cat([o, d, torch.full((B, 1), 2.0, device=DEV), torch.full((B, 1), 6.0, device=DEV),
-                      d / d.norm(dim=-1, keepdim=True)], -1).contiguous()
-    r = lambda *sh: torch.rand(*sh, generator=g).to(DEV)
-    n = lambda *sh: torch.randn(*sh, generator=g).to(DEV)
-    s = dict(emb=emb, table=emb.table.detach(), ws=ws, rays=rays, target=r(B, 3), t_rand=r(B, 64),
-             t_vals=torch.linspace(0., 1., 64, device=DEV), u={128: r(B, 128), 64: r(B, 64)},
-             noise_c=n(B, 64), noise_f={128: n(B, 192), 64: n(B, 128)})
-    _SCENES[B] = s
-    return s
+
+    draws = [("target", "rand", 3), ("t_rand", "rand", 64), (("u", 128), "rand", 128), (("u", 64), "rand", 64),
+             ("noise_c", "randn", 64), (("noise_f", 128), "randn", 192), (("noise_f", 64), "randn", 128)]
+    return small_scene(hn, ("resident", B), B, 300 + B, draws, half_space_density)
 
 
 def make_cfg(HF, s, v):
-    return HF.make_render_cfg(s["emb"].grid(), v["white"], False, v["noise"], n_importance=v["ni"], scatter="binned")
+    return HF.make_render_cfg(s.emb.grid(), v["white"], False, v["noise"], n_importance=v["ni"], scatter="binned")
 
 
 def forward(HF, s, v, form, rows=None, keep_feat=True, ws=None, wsb=None):
     """One render_fwd of the scene's rays (rows: a slice of them) in a form."""
     sl = slice(None) if rows is None else rows
     ni, noise = v["ni"], v["noise"]
-    B = s["rays"][sl].shape[0]
-    loss = dict(target=s["target"][sl], world=1, sparse_w=1e-3) if v["loss"] else None
-    out, st = HF.render_fwd(make_cfg(HF, s, v), s["rays"][sl], s["t_vals"], s["t_rand"][sl] if noise else None,
-                            s["u"][ni][sl], s["noise_c"][sl] if noise else None,
-                            s["noise_f"][ni][sl] if noise else None, s["table"], s["ws"] if ws is None else ws,
+    B = s.rays[sl].shape[0]
+    loss = dict(target=s.target[sl], world=1, sparse_w=1e-3) if v["loss"] else None
+    out, st = HF.render_fwd(make_cfg(HF, s, v), s.rays[sl], s.t_vals, s.t_rand[sl] if noise else None,
+                            s.u[ni][sl], s.noise_c[sl] if noise else None,
+                            s.noise_f[ni][sl] if noise else None, s.table, s.ws if ws is None else ws,
                             keep_feat, wsb=wsb, skip_dead_color=v["skip"], loss=loss, form=form)
     assert out["rgb"].shape == (B, 3)
     return out, st
@@ -107,18 +79,11 @@ def forward(HF, s, v, form, rows=None, keep_feat=True, ws=None, wsb=None):
 
 def workspace_marks(HF, st, B, v):
     """What the loss-mode forward leaves in its workspace for the backward: d
-    raw [B][64 + fine][4], the marks [B][4] u8 and the stamp (hn_render.hip's
-    layout: 2 packed nets | 256 x 4 dW slabs | [B][2048] coarse feature grads |
-    d raw [B][256][4] | marks | 8 count words, the stamp the aligned 8 bytes
-    within words 4-7)."""
-    L = HF.L
-    at = (2 * L.MLP_PACKED_FLOATS + 256 * 4 * L.MLP_PARAMS + B * 2048) * 4
-    draw = st.wsb[at:at + B * 256 * 16].view(torch.float32).view(B, 256, 4)[:, :64 + 64 + v["ni"]]
-    marks = st.wsb[at + B * 256 * 16:][:4 * B]
-    lmeta = at + B * 256 * 16 + 4 * B
-    pad = -(st.wsb.data_ptr() + lmeta + 16) % 8
-    stamp = st.wsb[lmeta + 16 + pad:][:8]
-    return draw.clone(), marks.clone(), stamp.clone()
+    raw [B][64 + fine][4], the marks [B][4] u8 and the stamp."""
+    at = ws_offsets(B)
+    draw = st.wsb[at.draw:at.marks].view(torch.float32).view(B, 256, 4)[:, :64 + 64 + v["ni"]]
+    marks = st.wsb[at.marks:at.lmeta]
+    return draw.clone(), marks.clone(), ws_stamp(st.wsb, B).clone()
 
 
 def stored_tiles(st, out, v):
@@ -136,18 +101,6 @@ def stored_tiles(st, out, v):
     f = torch.where(stored[..., None], feat[:, :8192].view(B, 8, 1024), 0)
     m = torch.where(stored[..., None], feat[:, 8192:].view(B, 8, 192), 0)
     return torch.cat([f.view(B, -1), m.view(B, -1)], 1), stored
-
-
-def backward(HF, s, out, st):
-    """The binned backward after a loss-mode forward: the loss value, the table
-    gradient and the ten NeRFSmall gradients."""
-    lo = torch.empty(4, device=DEV)
-    dws = HF.zeros_like_all(s["ws"])
-    d_table = torch.empty_like(s["table"])
-    loss = dict(target=s["target"], rgb=out["rgb"], rgb0=out["rgb0"], sparsity=out["sparsity"],
-                sparsity0=out["sparsity0"], tv=None, world=1, sparse_w=1e-3, tv_w=0.0, out=lo)
-    HF.render_bwd(st, {}, d_table, dws, overwrite=True, overwrite_mlp=True, loss=loss, prepass_done=True)
-    return [lo, d_table] + dws
 
 
 @pytest.mark.gpu
@@ -228,7 +181,7 @@ def test_resident_form_sees_repacked_weights(hn):
     B = 37
     s = scene(hn, B)
     v = dict(loss=False, ni=128, skip=False, noise=False, white=True)
-    ws = [w.clone() for w in s["ws"]]
+    ws = [w.clone() for w in s.ws]
     nbytes = hn._lib.lib().hn_render_workspace_bytes(make_cfg(HF, s, v), B)
     wsb = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)
     first, _ = forward(HF, s, v, "resident", ws=ws, wsb=wsb)
@@ -244,7 +197,7 @@ def test_resident_form_sees_repacked_weights(hn):
     assert bits_equal(st2.feat, st1.feat)
     assert not bits_equal(first["raw_c"], second["raw_c"]) and not bits_equal(first["raw_f"], second["raw_f"])
     # the packed copies a backward's repack leaves (weights_packed): the same launch without a packing kernel
-    third, _ = HF.render_fwd(make_cfg(HF, s, v), s["rays"], s["t_vals"], None, s["u"][128], None, None, s["table"], ws,
+    third, _ = HF.render_fwd(make_cfg(HF, s, v), s.rays, s.t_vals, None, s.u[128], None, None, s.table, ws,
                              False, wsb=wsb, weights_packed=True, form="resident")
     torch.cuda.synchronize()
     for k in OUT_KEYS:
@@ -266,8 +219,8 @@ def test_automatic_form_rule(hn):
     B = below + 1
     s = scene(hn, 256)
     idx = torch.arange(B, device=DEV) % 256
-    big = dict(s, rays=s["rays"][idx], target=s["target"][idx], t_rand=s["t_rand"][idx],
-               u={128: s["u"][128][idx]}, noise_c=None, noise_f={128: None})
+    big = SimpleNamespace(**dict(vars(s), rays=s.rays[idx], target=s.target[idx], t_rand=s.t_rand[idx],
+                                 u={128: s.u[128][idx]}, noise_c=None, noise_f={128: None}))
     v = dict(loss=False, ni=128, skip=True, noise=False, white=True)
     outs = [forward(HF, big, v, form, keep_feat=False)[0] for form in ("auto", "ring", "resident")]
     torch.cuda.synchronize()

@@ -16,7 +16,7 @@ import ctypes as C
 import pytest
 import torch
 
-from test_gpu_prepass_fused import bits_equal, forward, loss_of, scene, step_coeffs
+from gpu_support import bits_equal, forward_kind as forward, kind_scene as scene, loss_of, step_coeffs, ws_offsets
 
 pytestmark = pytest.mark.gpu
 
@@ -65,7 +65,7 @@ def test_job_draws_stand_alone_values_bitwise(hn, window, B):
     kernel (prepass_done, one more workgroup ahead of the lists')."""
     from hashnerf_pytorch_amd import functional as HF
     s = scene(hn, B, "rand")
-    cfg = HF.make_render_cfg(s["emb"].grid(), True, False, True, scatter="binned")
+    cfg = HF.make_render_cfg(s.emb.grid(), True, False, True, scatter="binned")
     cam = camera(hn, window)
     for n in WINDOWS[window][1]:
         for n_uni in (0, 2):
@@ -75,7 +75,7 @@ def test_job_draws_stand_alone_values_bitwise(hn, window, B):
                 out, st = forward(HF, s, cfg, fused, skip_dead=True)
                 nb = make_job(HF, cam, n, n_uni)
                 assert torch.cuda.default_generators[0].get_offset() == off_ref
-                HF.render_bwd(st, {}, torch.empty_like(s["table"]), HF.zeros_like_all(s["ws"]), overwrite=True,
+                HF.render_bwd(st, {}, torch.empty_like(s.table), HF.zeros_like_all(s.ws), overwrite=True,
                               overwrite_mlp=True, loss=loss_of(s, out, torch.empty(4, device=DEV)),
                               prepass_done=fused, next_batch=nb)
                 assert len(nb.out) == len(ref) == 2 + n_uni
@@ -89,17 +89,17 @@ def run_step(hn, HF, B, bin_cap, job):
     """One training step's backward (fused loss, table step, MLP steps, repack)
     on clones of the scene's parameters; everything it leaves behind."""
     s = scene(hn, B, "rand")
-    cfg = HF.make_render_cfg(s["emb"].grid(), True, False, True, scatter="binned")
+    cfg = HF.make_render_cfg(s.emb.grid(), True, False, True, scatter="binned")
     cfg.bin_cap = bin_cap
     g = torch.Generator().manual_seed(9)
-    ws = [w.clone() for w in s["ws"]]
-    table = s["table"].clone()
+    ws = [w.clone() for w in s.ws]
+    table = s.table.clone()
     m = (torch.rand(table.shape, generator=g) - 0.5).to(DEV) * 1e-3
     v = torch.rand(table.shape, generator=g).to(DEV) * 1e-6
     wm = [(torch.rand(w.shape, generator=g) - 0.5).to(DEV) * 1e-3 for w in ws]
     wv = [torch.rand(w.shape, generator=g).to(DEV) * 1e-6 for w in ws]
-    out, st = HF.render_fwd(cfg, s["rays"], s["t_vals"], s["t_rand"], s["u"], None, None, table, ws, True,
-                            skip_dead_color=True, loss=dict(target=s["target"], world=1, sparse_w=1e-3))
+    out, st = HF.render_fwd(cfg, s.rays, s.t_vals, s.t_rand, s.u, None, None, table, ws, True,
+                            skip_dead_color=True, loss=dict(target=s.target, world=1, sparse_w=1e-3))
     lo = torch.empty(4, device=DEV)
     dws = HF.zeros_like_all(ws)
     nb = make_job(HF, camera(hn, "crop20x13"), 37, 2) if job else None
@@ -107,7 +107,7 @@ def run_step(hn, HF, B, bin_cap, job):
                   table_step=(table, m, v, step_coeffs()), prepass_done=True,
                   mlp_step=[(p, a, b, step_coeffs()) for p, a, b in zip(ws, wm, wv)], repack=True, next_batch=nb)
     torch.cuda.synchronize()
-    packed = st.wsb[:2 * hn._lib.MLP_PACKED_FLOATS * 4].view(torch.float32).clone()
+    packed = st.wsb[:ws_offsets(B).slab].view(torch.float32).clone()
     return dict(lo=lo, table=table, m=m, v=v, packed=packed, ws=ws, wm=wm, wv=wv, dws=dws), nb
 
 
@@ -127,7 +127,7 @@ def test_step_with_job_bitwise(hn, B, bin_cap):
     for k in ("ws", "wm", "wv", "dws"):
         for i, (x, y) in enumerate(zip(a[k], b[k])):
             assert bits_equal(x, y), (k, i)
-    assert not bits_equal(a["table"], scene(hn, B, "rand")["table"])       # the step stepped
+    assert not bits_equal(a["table"], scene(hn, B, "rand").table)       # the step stepped
     for x, y in zip(nb.out, stand_alone(HF, camera(hn, "crop20x13"), 37, 2)):
         assert torch.equal(x, y)
 
@@ -208,13 +208,13 @@ def test_refused_job_queues_nothing(hn, case):
     from hashnerf_pytorch_amd import functional as HF
     B = 37
     s = scene(hn, B, "rand")
-    cfg = HF.make_render_cfg(s["emb"].grid(), True, False, True, scatter="atomic" if case == "atomic" else "binned")
+    cfg = HF.make_render_cfg(s.emb.grid(), True, False, True, scatter="atomic" if case == "atomic" else "binned")
     assert hn._lib.lib().hn_render_scatter_mode(cfg, B) == (1 if case == "atomic" else 2)
     cam = camera(hn, "crop20x13")
     out, st = forward(HF, s, cfg, False, skip_dead=False)
     nb = make_job(HF, cam, 20 * 13 + 1 if case == "n_rays" else 37, 2)
-    d_table = torch.full_like(s["table"], 7.0)
-    dws = HF.zeros_like_all(s["ws"])
+    d_table = torch.full_like(s.table, 7.0)
+    dws = HF.zeros_like_all(s.ws)
     lo = torch.full((4,), -1.0, device=DEV)
     with pytest.raises(RuntimeError, match=r"status 2"):
         HF.render_bwd(st, {}, d_table, dws, overwrite=True, overwrite_mlp=True, loss=loss_of(s, out, lo),

@@ -5,123 +5,19 @@ backward's work lists at 8 fine groups, the composite backward in the
 forward, the trainer and the refusals.
 
 Unless said otherwise T = 14, the blender box and rays as
-tests/test_gpu_scatter.py::_state makes them (restated here as _state64), and
+gpu_support.blender_state makes them, and
 every case ends with check_device_faults()."""
 import numpy as np
 import pytest
 import torch
 
 from conftest import golden, pcg_table
+from gpu_support import (MLP_KW, blender_state, bwd, close, done, g2t, golden_ni64, hf, mostly_close, rel_close,
+                         rel_err, scene_from_golden)
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-BOX = (torch.tensor([-4.0, -4.0, -3.4]), torch.tensor([4.0, 4.0, 3.3]))
 NAMES = ["render_ni64_white_perturb", "render_ni64_black_det"]
-MLP_KW = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-
-
-def _hf():
-    from importlib import import_module
-    return import_module("hashnerf_pytorch_amd.functional")
-
-
-def _done():
-    torch.cuda.synchronize()
-    _hf().L.check_device_faults()
-
-
-def golden_ni64(name):
-    g = golden(name)
-    g["table_grad"] = np.concatenate([g["table_grad"], golden(name + ".tg_hi")["table_grad_hi"]], 0)
-    return g
-
-
-def g2t(a, dev=DEV):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def close(a, b, rtol=1e-5, atol=1e-6, msg=""):
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
-
-
-def rel_err(a, b):
-    a = a.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(a) else np.asarray(a, np.float64)
-    b = b.detach().cpu().numpy().astype(np.float64) if torch.is_tensor(b) else np.asarray(b, np.float64)
-    return float(np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30))
-
-
-def rel_close(a, b, tol, msg):
-    err = rel_err(a, b)
-    assert err <= tol, f"{msg}: relative error {err:.3e}"
-
-
-def mostly_close(a, b, rtol, atol, frac, loose, msg):
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
-    a2, b2 = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
-    ok = np.isclose(a2, b2, rtol=rtol, atol=atol, equal_nan=True).all(-1)
-    assert ok.mean() >= frac, f"{msg}: only {ok.mean():.3f} of rays within tolerance"
-    np.testing.assert_allclose(a2, b2, rtol=0, atol=loose, err_msg=msg)
-
-
-def _scene_from_golden(hn, g):
-    emb = hn.HashEmbedder((g2t(g["box_min"], "cpu"), g2t(g["box_max"], "cpu")),
-                          log2_hashmap_size=int(g["log2T"]), finest_resolution=int(g["finest"])).to(DEV)
-    with torch.no_grad():
-        emb.table.copy_(g2t(pcg_table(g["table_seed"], g["log2T"])))
-    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
-    mc.load_state_dict({k[3:]: g2t(v) for k, v in g.items() if k.startswith("wc:")})
-    mf.load_state_dict({k[3:]: g2t(v) for k, v in g.items() if k.startswith("wf:")})
-    return emb, mc, mf
-
-
-def _state64(hn, B, T, seed, scatter="binned", ni=64, sigma_sign=0, keep_feat=True, skip_dead=False, det=False,
-             dense=False):
-    """tests/test_gpu_scatter.py::_state with the importance count as a parameter."""
-    HF = _hf()
-    torch.manual_seed(seed)
-    emb = hn.HashEmbedder(BOX, log2_hashmap_size=T, finest_resolution=512).to(DEV)
-    with torch.no_grad():
-        emb.table.uniform_(-0.5, 0.5)
-    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
-    if sigma_sign:   # sigma = w . relu(h): all weights of one sign fix the sign of every raw sigma
-        with torch.no_grad():
-            for m in (mc, mf):
-                w = m.sigma_net[1].weight
-                w[0] = sigma_sign * w[0].abs()
-    focal, K = hn.rays.blender_intrinsics(400, 400)
-    ro, rd = hn.get_rays(400, 400, K, hn.pose_spherical(30.0 + seed, -30.0, 4.0)[:3, :4].to(DEV))
-    sel = torch.randperm(400 * 400, device=DEV)[:B]
-    ro, rd = ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]
-    vd = rd / torch.norm(rd, dim=-1, keepdim=True)
-    rays = torch.cat([ro, rd, 2. * torch.ones_like(rd[:, :1]), 6. * torch.ones_like(rd[:, :1]), vd], -1)
-    g = torch.Generator(device=DEV).manual_seed(seed + 1)
-    t_rand = torch.rand((B, 64), device=DEV, generator=g)
-    u128 = torch.rand((B, 128), device=DEV, generator=g)
-    u = u128[:, :ni].contiguous()
-    if det:
-        t_rand, u = None, torch.linspace(0., 1., ni, device=DEV).expand(B, ni).contiguous()
-    t_vals = torch.linspace(0., 1., 64, device=DEV)
-    cfg = HF.make_render_cfg(emb.grid(), True, False, not det, n_importance=ni, scatter=scatter, dense_bwd=dense)
-    ws = list(mc.weights()) + list(mf.weights())
-    target = torch.rand((B, 3), device=DEV, generator=g)
-    s = dict(HF=HF, emb=emb, ws=ws, rays=rays, t_rand=t_rand, u=u, t_vals=t_vals, cfg=cfg, target=target)
-    s["out"], s["st"] = HF.render_fwd(cfg, rays, t_vals, t_rand, u, None, None, emb.table.detach(), ws, keep_feat,
-                                      skip_dead_color=skip_dead)
-    out = s["out"]
-    s["grads"] = dict(g_rgb=2. * (out["rgb"] - target) / (3 * B), g_rgb0=2. * (out["rgb0"] - target) / (3 * B),
-                      g_sparsity=torch.full((B,), 1e-3, device=DEV), g_sparsity0=torch.full((B,), 1e-3, device=DEV))
-    return s
-
-
-def _bwd(s, st=None):
-    HF = s["HF"]
-    d_table = torch.zeros_like(s["emb"].table)
-    dws = HF.zeros_like_all(s["ws"])
-    HF.render_bwd(st or s["st"], s["grads"], d_table, dws)
-    _done()
-    return d_table, dws
 
 
 # ---- 1. the fused path is taken -------------------------------------------------
@@ -130,9 +26,10 @@ def test_render_takes_the_fused_path_at_64(hn):
     holds a [64, 128] z_fine), for the blender-shaped fixture rays and for an
     LLFF-shaped call: 8 x 9 pixels from a pose, NDC rays, near 0 / far 1, raw
     noise 1.0 and the box from bbox_for_llff; all fine z lie in [0, 1]."""
-    HF = _hf()
+    HF = hf()
     g = golden_ni64(NAMES[0])
-    emb, mc, mf = _scene_from_golden(hn, g)
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     kw = dict(network_query_fn=hn.NetworkQuery(emb, hn.SHEncoder()), perturb=1., N_importance=64, network_fine=mf,
               N_samples=64, network_fn=mc, embed_fn=emb, use_viewdirs=True, white_bkgd=True, pytest=True)
     HF.LAST.clear()
@@ -161,7 +58,7 @@ def test_render_takes_the_fused_path_at_64(hn):
         assert bool(torch.isfinite(emb2.table.grad).all()) and torch.count_nonzero(emb2.table.grad) > 0
     finally:
         HF.DEBUG_KEEP = False
-    _done()
+    done()
 
 
 # ---- 2. the 64-sample merge ------------------------------------------------------
@@ -171,8 +68,8 @@ def test_fine_z_sort_structure_64(hn, det):
     fine z non-decreasing, each coarse index once in fine_src at its own value,
     the 64 others tagged 255, coarse first on ties (det: u = linspace(0, 1, 64)
     gives many exact ties)."""
-    s = _state64(hn, 259, 14, 23, det=det)
-    st = s["st"]
+    s = blender_state(hn, 259, 14, 23, ni=64, det=det)
+    st = s.st
     zf, zc, src = st.z_f.cpu(), st.z_c.cpu(), st.fine_src.cpu().long()
     assert tuple(zf.shape) == (259, 128) and tuple(src.shape) == (259, 128)
     assert (zf[:, 1:] >= zf[:, :-1]).all()
@@ -187,18 +84,18 @@ def test_fine_z_sort_structure_64(hn, det):
     prev = torch.cat([torch.full((zf.shape[0], 1), -1.0), zf[:, :-1]], 1)
     prev_tag = torch.cat([torch.zeros((zf.shape[0], 1), dtype=torch.long), src[:, :-1]], 1)
     assert not ((prev == zf) & coarse & (prev_tag == 255)).any()
-    _done()
+    done()
 
 
 # ---- 3. the coarse pass does not see the fine count --------------------------------
 def test_coarse_pass_independent_of_fine_count(hn):
-    a = _state64(hn, 259, 14, 7, ni=64, keep_feat=False)
-    b = _state64(hn, 259, 14, 7, ni=128, keep_feat=False)
-    assert torch.equal(a["rays"], b["rays"]) and torch.equal(a["t_rand"], b["t_rand"])
+    a = blender_state(hn, 259, 14, 7, ni=64, keep_feat=False)
+    b = blender_state(hn, 259, 14, 7, ni=128, keep_feat=False)
+    assert torch.equal(a.rays, b.rays) and torch.equal(a.t_rand, b.t_rand)
     for k in ("z_coarse", "raw_c", "rgb0", "depth0", "acc0", "sparsity0"):
-        assert torch.equal(a["out"][k], b["out"][k]), k
-    assert tuple(a["out"]["z_fine"].shape) == (259, 128) and tuple(b["out"]["z_fine"].shape) == (259, 192)
-    _done()
+        assert torch.equal(a.out[k], b.out[k]), k
+    assert tuple(a.out["z_fine"].shape) == (259, 128) and tuple(b.out["z_fine"].shape) == (259, 192)
+    done()
 
 
 # ---- 4. tight parity against the oracle on the device's z --------------------------
@@ -210,11 +107,12 @@ def _fused_vs_oracle(hn, oracle, g, ni, noise_seed=None, tol=None):
     seeded raw noise can be fed to both sides).  Returns the measured figures;
     asserts that test's tolerances (or tol's).
     (`same` leaves 3 % of the fine z out; test_gpu_sampling.py judges every importance sample.)"""
-    HF = _hf()
+    HF = hf()
     from hashnerf_pytorch_amd.render import _linspace_cached
     t = dict(out=(1e-4, 2e-5), raw=(1e-4, 1e-5), loss=1e-5, grad=5e-4, same=0.97)
     t.update(tol or {})
-    emb, mc, mf = _scene_from_golden(hn, g)
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     B = g["rays_o"].shape[0]
     rays_o, rays_d = g2t(g["rays_o"]), g2t(g["rays_d"])
     white, perturb = bool(g["white"]), float(g["perturb"])
@@ -269,7 +167,7 @@ def _fused_vs_oracle(hn, oracle, g, ni, noise_seed=None, tol=None):
     for w_dev, w_ref in ((mc.weights(), wc), (mf.weights(), wf)):
         for p, k in zip(w_dev, O.MLP_KEYS):
             rel_close(p.grad, w_ref[k].grad.numpy(), t["grad"], k)
-    _done()
+    done()
     return fig
 
 
@@ -299,12 +197,13 @@ def test_fused_step_vs_oracle_with_raw_noise(hn, oracle):
 def test_render_step_vs_reference_64(hn, name):
     """test_render_step_vs_reference (fused) on the 64 + 64 fixtures, its tolerances."""
     g = golden_ni64(name)
-    emb, mc, mf = _scene_from_golden(hn, g)
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     kw = dict(network_query_fn=hn.NetworkQuery(emb, hn.SHEncoder()), perturb=float(g["perturb"]), N_importance=64,
               network_fine=mf, N_samples=64, network_fn=mc, embed_fn=emb, use_viewdirs=True,
               white_bkgd=bool(g["white"]), raw_noise_std=0., ndc=False, lindisp=False, near=2., far=6., pytest=True)
     rays = torch.stack([g2t(g["rays_o"]), g2t(g["rays_d"])], 0)
-    HF = _hf()
+    HF = hf()
     HF.LAST.clear()
     HF.DEBUG_KEEP = True
     try:
@@ -326,7 +225,7 @@ def test_render_step_vs_reference_64(hn, name):
     for tag, m in (("c", mc), ("f", mf)):
         for k, p in m.named_parameters():
             rel_close(p.grad, g[f"g{tag}:{k}"], 3e-2, f"{tag}:{k}")
-    _done()
+    done()
 
 
 # ---- 6. the work lists at 8 fine groups ------------------------------------------------
@@ -338,8 +237,8 @@ def test_skip_equals_dense_64(hn, sign):
     gradients within 1e-5 (test_skip_extremes_match_dense's rule), all exact
     zeros for sign -1 -- then a forward with skip_dead_color and dense_bwd = 0
     gives the same table gradient bitwise."""
-    s = _state64(hn, 515, 16, 23, sigma_sign=sign)
-    st = s["st"]
+    s = blender_state(hn, 515, 16, 23, ni=64, sigma_sign=sign)
+    st = s.st
     sig = torch.cat([st.raw_c[..., 3].reshape(-1), st.raw_f[..., 3].reshape(-1)])
     if sign < 0:
         assert bool((sig <= 0).all())
@@ -350,7 +249,7 @@ def test_skip_equals_dense_64(hn, sign):
     res = {}
     for dense in (1, 0):
         st.cfg.dense_bwd = dense
-        res[dense] = _bwd(s)
+        res[dense] = bwd(s)
     st.cfg.dense_bwd = 0
     (td, wd), (ts, wsk) = res[1], res[0]
     assert torch.equal(td + 0.0, ts + 0.0), "table gradient: skipping changed it"
@@ -361,26 +260,26 @@ def test_skip_equals_dense_64(hn, sign):
             rel = float((a.double() - b.double()).norm() / a.double().norm().clamp_min(1e-30))
             assert rel <= 1e-5, f"gradient {k}: skipped vs dense relative {rel:.3e}"
     assert (torch.count_nonzero(ts) == 0) == (sign < 0)
-    s2 = _state64(hn, 515, 16, 23, sigma_sign=sign, skip_dead=True)
+    s2 = blender_state(hn, 515, 16, 23, ni=64, sigma_sign=sign, skip_dead=True)
     for k in ("rgb", "rgb0", "z_fine"):
-        assert torch.equal(s2["out"][k], s["out"][k]), k
-    t2, _ = _bwd(s2)
+        assert torch.equal(s2.out[k], s.out[k]), k
+    t2, _ = bwd(s2)
     assert torch.equal(t2 + 0.0, ts + 0.0), "table gradient: skip_dead_color changed it"
 
 
 # ---- 7. repeatable ------------------------------------------------------------------------
 def test_repeatable_64(hn):
-    s = _state64(hn, 515, 14, 3)
-    t1, w1 = _bwd(s)
-    t2, w2 = _bwd(s)
+    s = blender_state(hn, 515, 14, 3, ni=64)
+    t1, w1 = bwd(s)
+    t2, w2 = bwd(s)
     assert torch.count_nonzero(t1) > 0
     assert torch.equal(t1, t2)
     for x, y in zip(w1, w2):
         assert torch.equal(x, y)
-    s2 = _state64(hn, 515, 14, 3)
-    for a, b in ((s["st"].z_f, s2["st"].z_f), (s["st"].raw_f, s2["st"].raw_f), (s["st"].fine_src, s2["st"].fine_src)):
+    s2 = blender_state(hn, 515, 14, 3, ni=64)
+    for a, b in ((s.st.z_f, s2.st.z_f), (s.st.raw_f, s2.st.raw_f), (s.st.fine_src, s2.st.fine_src)):
         assert torch.equal(a, b)
-    _done()
+    done()
 
 
 # ---- 8. the composite backward in the forward ---------------------------------------------
@@ -389,25 +288,25 @@ def test_fused_prepass_matches_separate_64(hn, noise):
     """render_fwd(loss=...) + render_bwd(prepass_done=True) against the
     pre-pass form (B = 515): table and NeRFSmall gradients bitwise, the loss
     value within 1e-6 (test_fused_loss_backward_matches_separate's bound)."""
-    HF = _hf()
-    s = _state64(hn, 515, 14, 11, keep_feat=False)
+    HF = hf()
+    s = blender_state(hn, 515, 14, 11, ni=64, keep_feat=False)
     B = 515
     g = torch.Generator().manual_seed(5)
     nc = torch.randn(B, 64, generator=g).to(DEV) if noise else None
     nf = torch.randn(B, 128, generator=g).to(DEV) if noise else None
-    table = s["emb"].table.detach()
+    table = s.emb.table.detach()
     res = []
     for fused in (False, True):
-        loss_in = dict(target=s["target"], world=1, sparse_w=1e-3) if fused else None
-        out, st = HF.render_fwd(s["cfg"], s["rays"], s["t_vals"], s["t_rand"], s["u"], nc, nf, table, s["ws"], True,
-                                skip_dead_color=True, loss=loss_in)
+        loss_in = dict(target=s.target, world=1, sparse_w=1e-3) if fused else None
+        out, st = HF.render_fwd(s.cfg, s.rays, s.t_vals, s.t_rand, s.u, nc, nf, table, s.ws, True, skip_dead_color=True,
+                                loss=loss_in)
         lo = torch.empty(4, device=DEV)
         d_table = torch.empty_like(table)
-        dws = HF.zeros_like_all(s["ws"])
+        dws = HF.zeros_like_all(s.ws)
         HF.render_bwd(st, {}, d_table, dws, overwrite=True, overwrite_mlp=True, prepass_done=fused,
-                      loss=dict(target=s["target"], rgb=out["rgb"], rgb0=out["rgb0"], sparsity=out["sparsity"],
+                      loss=dict(target=s.target, rgb=out["rgb"], rgb0=out["rgb0"], sparsity=out["sparsity"],
                                 sparsity0=out["sparsity0"], tv=None, world=1, sparse_w=1e-3, tv_w=0.0, out=lo))
-        _done()
+        done()
         res.append((d_table, dws, lo, out))
     a, b = res
     assert torch.count_nonzero(a[0]) > 0
@@ -447,7 +346,7 @@ def test_trainer_explicit_matches_autograd_64(hn):
     assert float((te - ta).norm() / ta.norm()) < 1e-5
     for x, y in zip(we, wa):
         torch.testing.assert_close(x, y, rtol=1e-5, atol=1e-8)
-    _done()
+    done()
 
 
 _TRAJ = {}
@@ -463,7 +362,7 @@ def _trajectory(hn, off=None):
         setattr(tr, off, False)
     torch.manual_seed(11)
     losses = [float(tr.step()[0]) for _ in range(8)]
-    _done()
+    done()
     t = tr.embed_fn.table
     ost = tr.optimizer.state
     ws = tr.kw_train["network_fn"].weights() + tr.kw_train["network_fine"].weights()
@@ -491,27 +390,27 @@ def test_refusals_64(hn):
     """scatter="atomic" at 64: the training forward raises before a launch, the
     inference forward runs and equals the binned cfg's outputs bitwise; widths
     that do not match the cfg raise ValueError; render_image names N_importance."""
-    HF = _hf()
-    s = _state64(hn, 37, 14, 5, keep_feat=False)
-    cfg_a = HF.make_render_cfg(s["emb"].grid(), True, False, True, n_importance=64, scatter="atomic")
-    table = s["emb"].table.detach()
-    fwd = lambda cfg, keep, u=s["u"], nf=None: HF.render_fwd(cfg, s["rays"], s["t_vals"], s["t_rand"], u, None, nf,
-                                                             table, s["ws"], keep)
+    HF = hf()
+    s = blender_state(hn, 37, 14, 5, ni=64, keep_feat=False)
+    cfg_a = HF.make_render_cfg(s.emb.grid(), True, False, True, n_importance=64, scatter="atomic")
+    table = s.emb.table.detach()
+    fwd = lambda cfg, keep, u=s.u, nf=None: HF.render_fwd(cfg, s.rays, s.t_vals, s.t_rand, u, None, nf, table, s.ws,
+                                                          keep)
     with pytest.raises((ValueError, RuntimeError)):
         fwd(cfg_a, True)
     out_a, st_a = fwd(cfg_a, False)
     assert st_a is None
-    for k, v in s["out"].items():
+    for k, v in s.out.items():
         assert torch.equal(v.view(torch.int32), out_a[k].view(torch.int32)), k
     with pytest.raises(ValueError, match="u must be"):
-        fwd(s["cfg"], False, u=torch.rand(37, 128, device=DEV))
+        fwd(s.cfg, False, u=torch.rand(37, 128, device=DEV))
     with pytest.raises(ValueError, match="noise_f must be"):
-        fwd(s["cfg"], False, nf=torch.zeros(37, 192, device=DEV))
-    out, st = fwd(s["cfg"], True)
+        fwd(s.cfg, False, nf=torch.zeros(37, 192, device=DEV))
+    out, st = fwd(s.cfg, True)
     with pytest.raises(ValueError, match="g_raw_f must be"):
         HF.render_bwd(st, dict(g_raw_f=torch.zeros(37, 192, 4, device=DEV)), torch.zeros_like(table),
-                      HF.zeros_like_all(s["ws"]))
-    emb = s["emb"]
+                      HF.zeros_like_all(s.ws))
+    emb = s.emb
     mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
     _, K = hn.rays.blender_intrinsics(6, 5)
     with pytest.raises(ValueError, match="N_importance"):
@@ -519,14 +418,14 @@ def test_refusals_64(hn):
                         network_query_fn=hn.NetworkQuery(emb, hn.SHEncoder()), network_fn=mc, network_fine=mf,
                         N_samples=64, N_importance=64, perturb=0., raw_noise_std=0., ndc=False, use_viewdirs=True,
                         near=2., far=6.)
-    _done()
+    done()
 
 
 @pytest.mark.parametrize("B", [1, 3])
 def test_edge_sizes_64(hn, B):
-    s = _state64(hn, B, 14, 9)
-    t, ws = _bwd(s)
-    for k, v in s["out"].items():
+    s = blender_state(hn, B, 14, 9, ni=64)
+    t, ws = bwd(s)
+    for k, v in s.out.items():
         if k not in ("depth", "depth0"):      # an empty ray's depth is 0 / 0
             assert bool(torch.isfinite(v).all()), k
     assert bool(torch.isfinite(t).all()) and all(bool(torch.isfinite(w).all()) for w in ws)

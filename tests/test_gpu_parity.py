@@ -11,18 +11,10 @@ import pytest
 import torch
 
 from conftest import golden, pcg_table
+from gpu_support import MLP_KW, close, g2t, hf, mostly_close, rel_close, scene_from_golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-
-
-def g2t(a, dev=DEV):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def close(a, b, rtol=1e-5, atol=1e-6, msg=""):
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
-    np.testing.assert_allclose(a, b, rtol=rtol, atol=atol, err_msg=msg)
 
 
 @pytest.mark.parametrize("name", ["encode_t12", "encode_t12_f1024"])
@@ -49,8 +41,7 @@ def test_sh_bitexact(hn):
 
 def test_nerf_small_fwd_bwd(hn):
     g = golden("mlp")
-    m = hn.NeRFSmall(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3,
-                     hidden_dim_color=64, input_ch=32, input_ch_views=16).to(DEV)
+    m = hn.NeRFSmall(**MLP_KW).to(DEV)
     m.load_state_dict({k[2:]: g2t(v) for k, v in g.items() if k.startswith("w:")})
     x = g2t(g["x"]).requires_grad_(True)
     out = m(x)
@@ -81,8 +72,7 @@ def test_raw2outputs(hn, white):
 
 def test_sample_pdf(hn):
     g = golden("sample_pdf")
-    from importlib import import_module
-    HF = import_module("hashnerf_pytorch_amd.functional")
+    HF = hf()
     # the pdf normaliser restates torch's CPU summation order and the cdf its
     # fp64 cumsum, so given identical weights the samples are bit-identical
     s = HF.sample_pdf(g2t(g["bins"]), g2t(g["weights"]), g2t(g["u"])).cpu().numpy()
@@ -92,25 +82,13 @@ def test_sample_pdf(hn):
     np.testing.assert_array_equal(sd, g["samples_det"])
 
 
-def _scene_from_golden(hn, g):
-    emb = hn.HashEmbedder((g2t(g["box_min"], "cpu"), g2t(g["box_max"], "cpu")),
-                          log2_hashmap_size=int(g["log2T"]), finest_resolution=int(g["finest"])).to(DEV)
-    with torch.no_grad():
-        emb.table.copy_(g2t(pcg_table(g["table_seed"], g["log2T"])))
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    mc, mf = hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)
-    mc.load_state_dict({k[3:]: g2t(v) for k, v in g.items() if k.startswith("wc:")})
-    mf.load_state_dict({k[3:]: g2t(v) for k, v in g.items() if k.startswith("wf:")})
-    return emb, mc, mf
-
-
 @pytest.mark.parametrize("name", ["render_white_perturb", "render_black_det"])
 @pytest.mark.parametrize("fused", [True, False])
 def test_render_step_vs_reference(hn, name, fused):
     """One training step (render + loss + backward) against the reference."""
     g = golden(name)
-    emb, mc, mf = _scene_from_golden(hn, g)
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     sh = hn.SHEncoder()
     nq = hn.NetworkQuery(emb, sh) if fused else (
         lambda inputs, viewdirs, fn: hn.run_network(inputs, viewdirs, fn, emb, sh))
@@ -146,10 +124,10 @@ def test_fused_step_vs_oracle_on_device_z(hn, oracle, name):
     of the reference (sample_pdf's threshold) is factored out; the samples
     themselves are checked against the oracle's on the same inputs.
     (That check leaves 3 % of the fine z out; test_gpu_sampling.py judges every importance sample.)"""
-    from importlib import import_module
-    HF = import_module("hashnerf_pytorch_amd.functional")
+    HF = hf()
     g = golden(name)
-    emb, mc, mf = _scene_from_golden(hn, g)
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     nq = hn.NetworkQuery(emb, hn.SHEncoder())
     B = g["rays_o"].shape[0]
     rays_o, rays_d = g2t(g["rays_o"]), g2t(g["rays_d"])
@@ -196,22 +174,6 @@ def test_fused_step_vs_oracle_on_device_z(hn, oracle, name):
             rel_close(p.grad, w_ref[k].grad.numpy(), 5e-4, k)
 
 
-def mostly_close(a, b, rtol, atol, frac, loose, msg):
-    a = a.detach().cpu().numpy() if torch.is_tensor(a) else a
-    a2, b2 = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
-    ok = np.isclose(a2, b2, rtol=rtol, atol=atol, equal_nan=True).all(-1)
-    assert ok.mean() >= frac, f"{msg}: only {ok.mean():.3f} of rays within tolerance"
-    np.testing.assert_allclose(a2, b2, rtol=0, atol=loose, err_msg=msg)
-
-
-def rel_close(a, b, tol, msg):
-    """||a - b|| <= tol * ||b|| (gradients: summation order of float atomics)."""
-    a = a.detach().cpu().numpy().astype(np.float64)
-    b = b.astype(np.float64)
-    err = np.linalg.norm(a - b) / max(np.linalg.norm(b), 1e-30)
-    assert err <= tol, f"{msg}: relative error {err:.3e}"
-
-
 def test_fused_matches_unfused_large(hn):
     """Config-2-like shapes (T=19, finest 512): the fused kernels agree with the
     op-by-op HIP path on the same inputs, and everything stays finite."""
@@ -220,9 +182,7 @@ def test_fused_matches_unfused_large(hn):
     emb = hn.HashEmbedder(box, log2_hashmap_size=19, finest_resolution=512).to(DEV)
     with torch.no_grad():
         emb.table.uniform_(-0.5, 0.5)
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    mc, mf = hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)
+    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
     B = 1024
     cams = hn.rays.blender_cameras(8)
     focal, K = hn.rays.blender_intrinsics(400, 400)
@@ -257,9 +217,8 @@ def test_fused_matches_unfused_large(hn):
 @pytest.mark.parametrize("finest", [512, 1024])
 def test_tv_all_levels_vs_reference(hn, finest):
     """hn_tv_fwd/bwd (one launch each) against loss.py:11-43 per level."""
-    from importlib import import_module
-    HF = import_module("hashnerf_pytorch_amd.functional")
-    HL = import_module("hashnerf_pytorch_amd.loss")
+    HF = hf()
+    from hashnerf_pytorch_amd import loss as HL
     g = golden(f"tv_f{finest}")
     tab = g2t(pcg_table(g["table_seed"], g["log2T"])).requires_grad_(True)
     cubes, _ = HL.draw_tv_cubes(16, 16, finest)
@@ -296,7 +255,8 @@ def test_render_image_from_c2w_vs_reference(hn):
     inference (no grad: features not kept), det sampling, against the
     reference's render on the same scene."""
     g = golden("render_image")
-    emb, mc, mf = _scene_from_golden(hn, g)
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     H, W = int(g["H"]), int(g["W"])
     kw = dict(network_query_fn=hn.NetworkQuery(emb, hn.SHEncoder()), perturb=0., N_importance=128,
               network_fine=mf, N_samples=64, network_fn=mc, embed_fn=emb, use_viewdirs=True,
@@ -328,8 +288,7 @@ def test_fused_step_bbox_tighter_than_samples(hn, oracle, box):
     importance samples, sparsity weight raised to 1e-3 so its gradient
     counts.
     (The samples' own check leaves 3 % of the fine z out; test_gpu_sampling.py judges every importance sample.)"""
-    from importlib import import_module
-    HF = import_module("hashnerf_pytorch_amd.functional")
+    HF = hf()
     O = oracle
     torch.manual_seed(3)
     B, T, sparse_w = 64, 14, 1e-3
@@ -337,9 +296,7 @@ def test_fused_step_bbox_tighter_than_samples(hn, oracle, box):
     emb = hn.HashEmbedder((bmin, bmax), log2_hashmap_size=T, finest_resolution=512).to(DEV)
     with torch.no_grad():
         emb.table.uniform_(-0.3, 0.3)
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    mc, mf = hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)
+    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
     focal, K = hn.rays.blender_intrinsics(64, 64)
     ro, rd = hn.get_rays(64, 64, K, hn.pose_spherical(40.0, -35.0, 4.0)[:3, :4].to(DEV))
     sel = torch.randperm(64 * 64, device=DEV)[:B]

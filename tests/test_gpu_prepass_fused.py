@@ -12,98 +12,33 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import pcg_table
+from gpu_support import (SMALL_BOX, SMALL_FINEST as FINEST, SMALL_T as T, backward_after_loss_forward, bits_equal,
+                         forward_kind as forward, kind_scene as scene, loss_of, step_coeffs)
 
 DEV = torch.device("cuda:0")
-T, FINEST = 14, 64
 BS = (1, 5, 37, 256)
 KINDS = ("rand", "dead", "live")   # about half of the samples dead, all raw sigma <= 0, all > 0
 FAULT_PREPASS = 128
-
-_SCENES = {}
-
-
-def bits_equal(a, b):
-    """torch.equal on the bit patterns (a NaN depth of an empty ray compares equal to itself)."""
-    if a.dtype == torch.float32:
-        a, b = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
-    return a.shape == b.shape and torch.equal(a, b)
-
-
-def scene(hn, B, kind, noise=False):
-    """Rays, targets, draws, table and the two nets (built once per case and
-    left unchanged): the random tables test_gpu_parity.py uses; `dead` / `live`
-    give sigma_net's density row one sign (its inputs are ReLU outputs)."""
-    key = (B, kind, noise)
-    if key in _SCENES:
-        return _SCENES[key]
-    g = torch.Generator().manual_seed(100 + B)
-    box = (torch.tensor([-1.5, -1.5, -1.5]), torch.tensor([1.5, 1.5, 1.5]))
-    emb = hn.HashEmbedder(box, log2_hashmap_size=T, finest_resolution=FINEST).to(DEV)
-    with torch.no_grad():
-        emb.table.copy_(torch.from_numpy(pcg_table(7, T)).to(DEV))
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    torch.manual_seed(5)
-    nets = [hn.NeRFSmall(**kw).to(DEV), hn.NeRFSmall(**kw).to(DEV)]
-    if kind != "rand":
-        with torch.no_grad():
-            for n in nets:
-                row = n.sigma_net[1].weight[0]
-                row.copy_(row.abs().clamp_min(1e-3) * (-1.0 if kind == "dead" else 1.0))
-    ws = [w.detach() for n in nets for w in n.weights()]
-    _, K = hn.rays.blender_intrinsics(100, 100)
-    c2w = hn.pose_spherical(30.0, -30.0, 4.0)
-    ro, rd = hn.get_rays(100, 100, K, c2w[:3, :4].to(DEV))
-    sel = torch.randperm(100 * 100, generator=g)[:B].to(DEV)
-    o, d = ro.reshape(-1, 3)[sel], rd.reshape(-1, 3)[sel]
-    rays = torch.cat([o, d, torch.full((B, 1), 2.0, device=DEV), torch.full((B, 1), 6.0, device=DEV),
-                      d / d.norm(dim=-1, keepdim=True)], -1).contiguous()
-    s = dict(emb=emb, table=emb.table.detach(), ws=ws, rays=rays,
-             target=torch.rand(B, 3, generator=g).to(DEV), t_rand=torch.rand(B, 64, generator=g).to(DEV),
-             u=torch.rand(B, 128, generator=g).to(DEV),
-             t_vals=torch.linspace(0., 1., 64, device=DEV),
-             noise_c=torch.randn(B, 64, generator=g).to(DEV) if noise else None,
-             noise_f=torch.randn(B, 192, generator=g).to(DEV) if noise else None)
-    _SCENES[key] = s
-    return s
-
-
-def forward(HF, s, cfg, fused, skip_dead, wsb=None):
-    loss = dict(target=s["target"], world=1, sparse_w=1e-3) if fused else None
-    return HF.render_fwd(cfg, s["rays"], s["t_vals"], s["t_rand"], s["u"], s["noise_c"], s["noise_f"], s["table"],
-                         s["ws"], True, wsb=wsb, skip_dead_color=skip_dead, loss=loss)
-
-
-def loss_of(s, out, lo):
-    return dict(target=s["target"], rgb=out["rgb"], rgb0=out["rgb0"], sparsity=out["sparsity"],
-                sparsity0=out["sparsity0"], tv=None, world=1, sparse_w=1e-3, tv_w=0.0, out=lo)
-
-
-def step_coeffs():
-    return {"beta1": 0.9, "beta2": 0.99, "one_minus_beta1": 1 - 0.9, "one_minus_beta2": 1 - 0.99, "eps": 1e-15,
-            "neg_wd_lr": 0.0, "neg_step_lr": -1e-2, "mode": 2, "has_wd": 0}
-
 
 def run_pair(hn, B, kind, white, dense, noise=False):
     """(separate, fused) results of one case: loss value, table gradient, the
     ten NeRFSmall gradients, and the table / m / v after a fused table step."""
     from hashnerf_pytorch_amd import functional as HF
     s = scene(hn, B, kind, noise)
-    cfg = HF.make_render_cfg(s["emb"].grid(), white, False, True, scatter="binned", dense_bwd=bool(dense))
+    cfg = HF.make_render_cfg(s.emb.grid(), white, False, True, scatter="binned", dense_bwd=bool(dense))
     assert hn._lib.lib().hn_render_scatter_mode(cfg, B) == 2
     g = torch.Generator().manual_seed(9)
-    m0 = (torch.rand(s["table"].shape, generator=g) - 0.5).to(DEV) * 1e-3
-    v0 = torch.rand(s["table"].shape, generator=g).to(DEV) * 1e-6
+    m0 = (torch.rand(s.table.shape, generator=g) - 0.5).to(DEV) * 1e-3
+    v0 = torch.rand(s.table.shape, generator=g).to(DEV) * 1e-6
     res = []
     for fused in (False, True):
         r = {}
         for stepped in (False, True):
             out, st = forward(HF, s, cfg, fused, skip_dead=not dense and not noise)
             lo = torch.empty(4, device=DEV)
-            dws = HF.zeros_like_all(s["ws"])
-            d_table = None if stepped else torch.empty_like(s["table"])
-            p, m, v = s["table"].clone(), m0.clone(), v0.clone()
+            dws = HF.zeros_like_all(s.ws)
+            d_table = None if stepped else torch.empty_like(s.table)
+            p, m, v = s.table.clone(), m0.clone(), v0.clone()
             HF.render_bwd(st, {}, d_table, dws, overwrite=True, overwrite_mlp=True, loss=loss_of(s, out, lo),
                           table_step=(p, m, v, step_coeffs()) if stepped else None, prepass_done=fused)
             torch.cuda.synchronize()
@@ -156,7 +91,7 @@ def test_loss_mode_forward_outputs_unchanged(hn, B, kind):
     acc, sparsity (both passes), z_std, raw, z, fine_src, features and masks."""
     from hashnerf_pytorch_amd import functional as HF
     s = scene(hn, B, kind)
-    cfg = HF.make_render_cfg(s["emb"].grid(), True, False, True, scatter="binned")
+    cfg = HF.make_render_cfg(s.emb.grid(), True, False, True, scatter="binned")
     (oa, sa), (ob, sb) = (forward(HF, s, cfg, fused, skip_dead=False) for fused in (False, True))
     torch.cuda.synchronize()
     assert set(oa) == set(ob) and len(oa) == 13
@@ -215,7 +150,7 @@ def _forge(HF, st, s):
     """Make functional.render_bwd believe st's forward ran with the loss, so
     that the device-side stamp check is what refuses the call."""
     import weakref
-    st.prepass_done = (s["target"].data_ptr(), 1.0, 1e-3)
+    st.prepass_done = (s.target.data_ptr(), 1.0, 1e-3)
     HF._PREPASS_ON_WS[st.wsb.data_ptr()] = weakref.ref(st)
 
 
@@ -228,15 +163,14 @@ def test_prepass_done_guards(hn, monkeypatch):
     from hashnerf_pytorch_amd import functional as HF
     B = 37
     s, s5 = scene(hn, B, "rand"), scene(hn, 5, "rand")
-    cfg = HF.make_render_cfg(s["emb"].grid(), True, False, True, scatter="binned")
+    cfg = HF.make_render_cfg(s.emb.grid(), True, False, True, scatter="binned")
     nbytes = hn._lib.lib().hn_render_workspace_bytes(cfg, B)
     wsb = torch.zeros(nbytes, dtype=torch.uint8, device=DEV)   # no stale stamp in recycled memory
     monkeypatch.setattr(HF, "CHECK_FAULTS", False)
     assert _read_faults(hn) == 0
 
     def backward(st, out):
-        HF.render_bwd(st, {}, torch.empty_like(s["table"]), HF.zeros_like_all(s["ws"]), overwrite=True,
-                      overwrite_mlp=True, loss=loss_of(s, out, torch.empty(4, device=DEV)), prepass_done=True)
+        backward_after_loss_forward(HF, s, out, st)
 
     # 1. a plain forward
     out, st = forward(HF, s, cfg, False, True, wsb=wsb)
@@ -277,8 +211,7 @@ def test_prepass_abi_validation_without_gpu(hn):
     L = hn._lib
     lib = L.lib()
     HF = hn.functional
-    box = (torch.tensor([-1.5, -1.5, -1.5]), torch.tensor([1.5, 1.5, 1.5]))
-    emb = hn.HashEmbedder(box, log2_hashmap_size=T, finest_resolution=FINEST)
+    emb = hn.HashEmbedder(SMALL_BOX, log2_hashmap_size=T, finest_resolution=FINEST)
     cfg = HF.make_render_cfg(emb.grid(), True, False, False, scatter="binned")
     cfg_a = HF.make_render_cfg(emb.grid(), True, False, False, scatter="atomic")
     x = 16   # never dereferenced

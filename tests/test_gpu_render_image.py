@@ -8,36 +8,18 @@ import pytest
 import torch
 
 from conftest import golden, pcg_table
+from gpu_support import MLP_KW, g2t, mostly_close, scene_from_golden
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
-MLP_KW = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-
-
-def g2t(a, dev=DEV):
-    return torch.from_numpy(np.ascontiguousarray(a)).to(dev)
-
-
-def mostly_close(a, b, rtol, atol, frac, loose, msg):
-    a = a.detach().cpu().numpy()
-    a2, b2 = a.reshape(a.shape[0], -1), b.reshape(b.shape[0], -1)
-    ok = np.isclose(a2, b2, rtol=rtol, atol=atol, equal_nan=True).all(-1)
-    assert ok.mean() >= frac, f"{msg}: only {ok.mean():.3f} of rays within tolerance"
-    np.testing.assert_allclose(a2, b2, rtol=0, atol=loose, err_msg=msg)
 
 
 @pytest.fixture(scope="module")
 def fixture_scene(hn):
     """The reference's 12 x 14 render (168 rays: 42 ray groups, no multiple of 8)."""
     g = golden("render_image")
-    emb = hn.HashEmbedder((g2t(g["box_min"], "cpu"), g2t(g["box_max"], "cpu")),
-                          log2_hashmap_size=int(g["log2T"]), finest_resolution=int(g["finest"])).to(DEV)
-    with torch.no_grad():
-        emb.table.copy_(g2t(pcg_table(g["table_seed"], g["log2T"])))
-    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
-    mc.load_state_dict({k[3:]: g2t(v) for k, v in g.items() if k.startswith("wc:")})
-    mf.load_state_dict({k[3:]: g2t(v) for k, v in g.items() if k.startswith("wf:")})
+    sc = scene_from_golden(hn, g)
+    emb, mc, mf = sc.emb, sc.mc, sc.mf
     kw = dict(network_query_fn=hn.NetworkQuery(emb, hn.SHEncoder()), perturb=0., N_importance=128,
               network_fine=mf, N_samples=64, network_fn=mc, embed_fn=emb, use_viewdirs=True,
               white_bkgd=True, raw_noise_std=0., ndc=False, lindisp=False, near=2., far=6., pytest=True)

@@ -10,7 +10,7 @@ Here every importance sample is judged in cdf space (tests/sampling_check.py:
 none of it measured on a kernel; test_sampling_check_cpu.py shows the oracle
 passes it and five kinds of sampler bug do not).
 
-States are built as test_gpu_scatter._state does (T = 14, finest 512, the
+States are built as gpu_support.blender_state does (T = 14, finest 512, the
 blender box and camera), with t_vals, t_rand and u made on the CPU and
 uploaded, so host and device see the same bits.  Bound settings
 (sampling_check.SETTINGS): uniform 2/6, per-ray near in [0.5, 3] / far in
@@ -36,50 +36,26 @@ The coarse z is bitwise on both branches, lindisp included.
 import pytest
 import torch
 
+from gpu_support import BLENDER_BOX, OUT_KEYS, bits_equal, blender_nets, hf, rel_err
 from sampling_check import SETTINGS, cdf_residual, coarse_z_ref, make_u, rank_residual, raw_weights_err, ray_bounds
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda"
 T = 14
-BOX = (torch.tensor([-4.0, -4.0, -3.4]), torch.tensor([4.0, 4.0, 3.3]))
-MLP_KW = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
+BOX = BLENDER_BOX
 SIGMA_SIGN = {"natural": 0, "zero": -1, "dense": 1}
 U_KINDS = ("random", "linspace", "edges")
-OUT_KEYS = ("rgb", "depth", "acc", "sparsity", "rgb0", "depth0", "acc0", "sparsity0", "z_std", "z_coarse", "z_fine",
-            "raw_c", "raw_f")
 _SCENES = {}
 _RAYS = {}
 
 
-def _hf():
-    from importlib import import_module
-    return import_module("hashnerf_pytorch_amd.functional")
-
-
-def bits_equal(a, b):
-    """torch.equal on the bit patterns (a NaN depth of an empty ray equals itself)."""
-    if a.dtype == torch.float32:
-        a, b = a.contiguous().view(torch.int32), b.contiguous().view(torch.int32)
-    return a.shape == b.shape and torch.equal(a, b)
-
-
 def scene(hn, weights):
-    """Table and nets of a kind of weights (test_gpu_scatter._state's sigma_sign:
-    -1 makes every raw sigma <= 0, a uniform pdf; +1 every one >= 0).  Built once."""
+    """Table and nets of a kind of weights (blender_nets' sigma_sign: -1 makes
+    every raw sigma <= 0, a uniform pdf; +1 every one >= 0).  Built once."""
     if weights not in _SCENES:
-        torch.manual_seed(31 + SIGMA_SIGN[weights])
-        emb = hn.HashEmbedder(BOX, log2_hashmap_size=T, finest_resolution=512).to(DEV)
-        with torch.no_grad():
-            emb.table.uniform_(-0.5, 0.5)
-        mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
-        if SIGMA_SIGN[weights]:
-            with torch.no_grad():
-                for m in (mc, mf):
-                    w = m.sigma_net[1].weight
-                    w[0] = SIGMA_SIGN[weights] * w[0].abs()
-        _SCENES[weights] = dict(emb=emb, mc=mc, mf=mf, table=emb.table.detach(),
-                                ws=[w.detach() for w in list(mc.weights()) + list(mf.weights())])
+        n = blender_nets(hn, T, 31 + SIGMA_SIGN[weights], sigma_sign=SIGMA_SIGN[weights])
+        _SCENES[weights] = dict(emb=n.emb, mc=n.mc, mf=n.mf, table=n.emb.table.detach(),
+                                ws=[w.detach() for w in list(n.mc.weights()) + list(n.mf.weights())])
     return _SCENES[weights]
 
 
@@ -99,7 +75,7 @@ def make_rays(hn, B, setting, seed=0):
 
 def forward(hn, rays, ni, lindisp, weights, u, t_rand, form=None):
     """One HF.render_fwd of CPU-made inputs; returns (out, state), the device fault word read."""
-    HF = _hf()
+    HF = hf()
     sc = scene(hn, weights)
     cfg = HF.make_render_cfg(sc["emb"].grid(), True, lindisp, t_rand is not None, n_importance=ni, scatter="binned")
     t_vals = torch.linspace(0., 1., 64)
@@ -247,7 +223,7 @@ def test_ties_and_unsorted_coarse_fallback(hn, oracle, ni, weights):
     "zero": the uniform pdf over decreasing bins), and on the ordinary rays in
     both cases.  Ordinary rays give the bits they give in a batch without the
     odd rays, in either form of the kernel."""
-    HF = _hf()
+    HF = hf()
     rays = make_rays(hn, 8, "uniform", seed=3).clone()
     rays[0, 6:8] = 4.0    # powers of two: near * (1 - t) + near * t is near exactly (the products are exact,
     rays[1, 6:8] = 2.0    # fl(1 - t) + t is within 2^-25 of 1 and rounds to it)
@@ -314,7 +290,7 @@ def test_sample_pdf_entry_edges(hn, n_bins, n_samples):
     bins decrease.  Not compared bitwise with torch on the CPU at these widths:
     ATen's row-sum order depends on the host's vector ISA
     (test_gpu_parity keeps the bitwise fixture)."""
-    HF = _hf()
+    HF = hf()
     B = 5
     g = torch.Generator().manual_seed(100 * n_bins + n_samples)
     worst = 0.0
@@ -337,7 +313,7 @@ def test_sample_pdf_entry_edges(hn, n_bins, n_samples):
 
 
 def test_sample_pdf_entry_no_samples(hn):
-    HF = _hf()
+    HF = hf()
     g = torch.Generator().manual_seed(3)
     bins = torch.sort(torch.rand(5, 9, generator=g), -1)[0]
     s = HF.sample_pdf(bins.to(DEV), torch.rand(5, 8, generator=g).to(DEV), torch.empty(5, 0, device=DEV))
@@ -355,13 +331,10 @@ def test_fused_step_lindisp_per_ray_bounds(hn, oracle):
     oracle's fine pass runs on the device's z_fine, whose samples
     test_every_importance_sample checks one by one."""
     import numpy as np
-    O, HF = oracle, _hf()
+    O, HF = oracle, hf()
     B = 67
-    torch.manual_seed(41)
-    emb = hn.HashEmbedder(BOX, log2_hashmap_size=T, finest_resolution=512).to(DEV)
-    with torch.no_grad():
-        emb.table.uniform_(-0.5, 0.5)
-    mc, mf = hn.NeRFSmall(**MLP_KW).to(DEV), hn.NeRFSmall(**MLP_KW).to(DEV)
+    n = blender_nets(hn, T, 41)
+    emb, mc, mf = n.emb, n.mc, n.mf
     rb = make_rays(hn, B, "lindisp_per_ray", seed=4)
     assert rb[:, 6].unique().numel() == B and rb[:, 7].unique().numel() == B
     nq = hn.NetworkQuery(emb, hn.SHEncoder())
@@ -396,12 +369,8 @@ def test_fused_step_lindisp_per_ray_bounds(hn, oracle):
     np.testing.assert_allclose(loss.item(), ref_loss.item(), rtol=1e-5, atol=1e-7)
     ref_loss.backward()
 
-    def rel(a, b):
-        a, b = a.detach().cpu().double(), b.detach().double()
-        return float(torch.linalg.norm(a - b) / max(float(torch.linalg.norm(b)), 1e-30))
-
     assert torch.count_nonzero(tab.grad) > 0
-    assert rel(emb.table.grad, tab.grad) <= 5e-4, rel(emb.table.grad, tab.grad)
+    assert rel_err(emb.table.grad, tab.grad) <= 5e-4, rel_err(emb.table.grad, tab.grad)
     for w_dev, w_ref in ((mc.weights(), wc), (mf.weights(), wf)):
         for p, k in zip(w_dev, O.MLP_KEYS):
-            assert rel(p.grad, w_ref[k].grad) <= 5e-4, (k, rel(p.grad, w_ref[k].grad))
+            assert rel_err(p.grad, w_ref[k].grad) <= 5e-4, (k, rel_err(p.grad, w_ref[k].grad))

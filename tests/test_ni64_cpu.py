@@ -10,16 +10,9 @@ import pytest
 import torch
 
 from conftest import GOLDEN, golden, pcg_table
+from gpu_support import MLP_KW, golden_ni64
 
 NAMES = ["render_ni64_white_perturb", "render_ni64_black_det"]
-
-
-def golden_ni64(name):
-    """make_golden_ni64.load_render_ni64: the table gradient's levels 8-15 live
-    in a second file (each committed file stays under 1 MiB)."""
-    g = golden(name)
-    g["table_grad"] = np.concatenate([g["table_grad"], golden(name + ".tg_hi")["table_grad_hi"]], 0)
-    return g
 
 
 def t(a):
@@ -163,9 +156,7 @@ def test_training_on_the_atomic_schedule_is_refused_before_any_launch(hn):
 def _nets(hn):
     box = (torch.tensor([-1.5, -1.5, -1.]), torch.tensor([1.5, 1.5, 1.]))
     emb = hn.HashEmbedder(box, log2_hashmap_size=14, finest_resolution=512)
-    kw = dict(num_layers=2, hidden_dim=64, geo_feat_dim=15, num_layers_color=3, hidden_dim_color=64,
-              input_ch=32, input_ch_views=16)
-    return hn.NetworkQuery(emb, hn.SHEncoder()), hn.NeRFSmall(**kw), hn.NeRFSmall(**kw)
+    return hn.NetworkQuery(emb, hn.SHEncoder()), hn.NeRFSmall(**MLP_KW), hn.NeRFSmall(**MLP_KW)
 
 
 def test_fusable_at_64_and_image_kernel_is_not(hn):
