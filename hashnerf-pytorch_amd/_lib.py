@@ -72,7 +72,13 @@ class HnImageArgs(C.Structure):
                 ("weights_packed", C.c_int32)]
 
 
-IMAGE_VARIANTS = {"reencode": 1, "row_major": 2}    # hn_render_image_variant's bits
+class HnViewArgs(C.Structure):
+    """hn_view_args: hn_render_views' arguments (u of the image member: [cfg.n_importance])."""
+    _fields_ = [("image", HnImageArgs), ("ndc", C.c_int32), ("ndc_sx", C.c_float), ("ndc_sy", C.c_float),
+                ("variant", C.c_int32)]
+
+
+IMAGE_VARIANTS = {"reencode": 1, "row_major": 2}    # hn_render_image_variant's and hn_view_args.variant's bits
 FWD_FORMS = {"auto": 0, "ring": 1, "resident": 2}   # hn_render_fwd_form's forms
 
 
@@ -194,6 +200,8 @@ SIGNATURES = {
     "hn_render_image": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), _P, C.c_size_t, _P]),
     "hn_render_image_variant": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), C.c_int32, _P,
                                             C.c_size_t, _P]),
+    "hn_render_views_workspace_bytes": (C.c_size_t, [C.POINTER(HnRenderCfg)]),
+    "hn_render_views": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnViewArgs), _P, C.c_size_t, _P]),
     "hn_render_bins": (C.c_int32, [C.POINTER(HnRenderCfg), C.c_int64, C.POINTER(C.c_int32)]),
     "hn_render_bwd_owner": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                         C.c_size_t, C.c_int32, C.c_int32, _P]),

@@ -2,8 +2,8 @@
 // training ray batch: the C entry points hn_render_fwd / hn_render_bwd, the
 // pre-pass kernel of both backward schedules (not launched by the binned one
 // after a training forward that did its work, hn_render_fwd_args.loss), and
-// the host side; and hn_render_image, the evaluation renderer (whole images
-// from poses, hn_render_image.h).  One
+// the host side; and hn_render_views / hn_render_image, the evaluation renderer
+// (whole images from poses, hn_render_image.h).  One
 // translation unit; the device code is in the headers (each says what it holds).
 #include "hn_render_args.h"   // kernel arguments, rays, feature cache, shared helpers
 #include "hn_render_fwd.h"    // render_fwd_kernel
@@ -118,7 +118,7 @@ static int32_t check_cfg(const hn_render_cfg* c) {
   if (c->dense_bwd < 0 || c->dense_bwd > 1) return HN_E_SHAPE;
   return HN_OK;
 }
-// The whole-image kernel renders 64 + 128 samples only
+// hn_render_image(_variant)'s own refusal: 64 + 128 samples only (hn_render_views takes both counts)
 static int32_t check_image_cfg(const hn_render_cfg* c) {
   const int32_t st = check_cfg(c);
   return st ? st : (c->n_importance != kNi ? HN_E_SHAPE : HN_OK);
@@ -365,7 +365,7 @@ static void launch_owner(const BinR& r, const BinGeom& bg, int n_bins, hipStream
                      (size_t)(2 << bg.shift) * sizeof(unsigned long long), s, r);
 }
 
-// What hn_render_fwd and hn_render_image share of their kernels' arguments; the
+// What hn_render_fwd and hn_render_views share of their kernels' arguments; the
 // nets' packed copies (Pc, Pf: their workspace's) are made here unless given
 static int32_t field_args(const hn_render_cfg* cfg, const float* t_vals, const float* u, const float* table,
                           const hn_mlp& coarse, const hn_mlp& fine, int32_t weights_packed, void* workspace,
@@ -505,7 +505,8 @@ extern "C" int32_t hn_render_fwd_form(const hn_render_cfg* cfg, const hn_render_
   return hip_status(hipGetLastError());
 }
 
-// Workspace of hn_render_image (offsets in floats): both nets' packed weights |
+// Workspace of hn_render_views / hn_render_image (offsets in floats; the fixed
+// grid's, so the same for both importance counts): both nets' packed weights |
 // one slot per wave of the persistent grid (its current ray's two coarse
 // feature tiles, ImageK::slots)
 struct ImageWs {
@@ -524,15 +525,32 @@ static ImageWs image_ws_layout() {
 extern "C" size_t hn_render_image_workspace_bytes(const hn_render_cfg* cfg) {
   return check_image_cfg(cfg) ? 0 : image_ws_layout().total * sizeof(float);
 }
+extern "C" size_t hn_render_views_workspace_bytes(const hn_render_cfg* cfg) {
+  return check_cfg(cfg) ? 0 : image_ws_layout().total * sizeof(float);
+}
 
-extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
-                                           void* workspace, size_t ws_bytes, void* stream) {
-  int32_t st = check_image_cfg(cfg);
-  if (st) return st;
+// render_image_kernel<kNiT, kNdc> of a cfg and a launch: the one place that picks the instantiation
+static void launch_image(const hn_render_cfg* cfg, hipStream_t s, const ImageK& k) {
+  const dim3 grid(kImgBlocks), block(64 * kImgBlockWaves);
+  with_bool(cfg->n_importance == kNi64, [&](auto kNi64T) {
+    with_bool(k.ndc != 0, [&](auto kNdc) {
+      constexpr int ni = decltype(kNi64T)::value ? kNi64 : kNi;
+      hipLaunchKernelGGL((render_image_kernel<ni, decltype(kNdc)::value>), grid, block, 0, s, k);
+    });
+  });
+}
+
+// The whole-image renderer behind hn_render_views and hn_render_image(_variant)
+// (cfg checked by the entry point, which has made its own refusals): every
+// check, then the launch
+static int32_t render_views(const hn_render_cfg* cfg, const hn_image_args* a, int32_t ndc, float ndc_sx,
+                            float ndc_sy, int32_t variant, void* workspace, size_t ws_bytes, void* stream) {
+  int32_t st;
   if (!a) return HN_E_NULL;
   if (cfg->perturb) return HN_E_SHAPE;   // the stratified jitter is the training forward's
   if (a->H <= 0 || a->W <= 0 || a->n_views < 0 || (a->pose_stride != 12 && a->pose_stride != 16)) return HN_E_SHAPE;
   if (variant < 0 || variant > (kImgReencode | kImgRowMajor)) return HN_E_SHAPE;
+  if (ndc < 0 || ndc > 1) return HN_E_SHAPE;
   if (a->n_views == 0) return HN_OK;
   if (!a->poses || !a->t_vals || !a->u || !a->table || !mlp_ok(a->coarse) || !mlp_ok(a->fine)) return HN_E_NULL;
   if (!a->rgb || !a->depth || !a->acc) return HN_E_NULL;
@@ -555,11 +573,27 @@ extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_im
   k.n_views = a->n_views; k.H = a->H; k.W = a->W; k.pose_stride = a->pose_stride;
   k.groups = (uint32_t)groups;
   k.fx = a->fx; k.fy = a->fy; k.cx = a->cx; k.cy = a->cy; k.near = a->near; k.far = a->far;
+  k.ndc = ndc; k.sx = ndc_sx; k.sy = ndc_sy;
   k.poses = a->poses;
   k.slots = (variant & kImgReencode) ? nullptr : ws_at<float>(workspace, L.slots);
   k.rgb = a->rgb; k.depth = a->depth; k.acc = a->acc; k.rays = a->rays;
-  hipLaunchKernelGGL(render_image_kernel, dim3(kImgBlocks), dim3(64 * kImgBlockWaves), 0, s, k);
+  launch_image(cfg, s, k);
   return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_render_views(const hn_render_cfg* cfg, const hn_view_args* a, void* workspace,
+                                   size_t ws_bytes, void* stream) {
+  const int32_t st = check_cfg(cfg);
+  if (st) return st;
+  if (!a) return HN_E_NULL;
+  return render_views(cfg, &a->image, a->ndc, a->ndc_sx, a->ndc_sy, a->variant, workspace, ws_bytes, stream);
+}
+
+extern "C" int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
+                                           void* workspace, size_t ws_bytes, void* stream) {
+  const int32_t st = check_image_cfg(cfg);
+  if (st) return st;
+  return render_views(cfg, a, 0, 0.f, 0.f, variant, workspace, ws_bytes, stream);
 }
 
 extern "C" int32_t hn_render_image(const hn_render_cfg* cfg, const hn_image_args* a, void* workspace,

@@ -2,9 +2,10 @@
 // (run_nerf_helpers.py:310-392 render() under render_path, :395-459), one
 // launch for a list of views.  A persistent grid of the training forward's
 // 4-wave workgroups: every wave loops over rays -- the pixel's ray made here
-// from the pose and K (pixel_ray, the samplers' arithmetic), then the forward's
-// own passes from the same device functions (render_fwd_kernel's results bit
-// for bit) -- and writes rgb, depth and acc only.  Nothing is saved for a
+// from the pose and K (pixel_ray, the samplers' arithmetic; then ndc_ray where
+// the launch asks for NDC rays), then the forward's own passes from the same
+// device functions (render_fwd_kernel's results bit for bit, at 64 + 128 or
+// 64 + 64 samples) -- and writes rgb, depth and acc only.  Nothing is saved for a
 // backward: z, raw and the samples' coarse origins live in LDS, the two coarse
 // feature tiles a fine pass takes its coarse twins from in a slot of the
 // workspace that the wave owns for the whole launch.
@@ -40,6 +41,8 @@ struct ImageK {
   uint32_t Hb, Wb;       // the image in 2 x 2 pixel blocks
   uint32_t groups;       // ray groups (4 rays) of the launch
   float fx, fy, cx, cy, near, far;
+  int ndc;               // 1: the pixel's ray goes through ndc_ray (hn_view_args.ndc)
+  float sx, sy;          // ... with these factors
   const float* poses;
   float* slots;          // [4 kImgBlocks][kImgSlotFloats], or NULL: every fine sample encoded
   float *rgb, *depth, *acc, *rays;
@@ -53,6 +56,8 @@ struct ImagePix {
   float fx, fy, cx, cy, near, far;
   int H, W, pose_stride, variant;
   uint32_t Hb, Wb;
+  int ndc;
+  float sx, sy;
   const float* poses;
   float *rgb, *depth, *acc, *rays;
 };
@@ -108,9 +113,15 @@ struct ImageTiles {
 
 HN_DEV float wave_uniform(float v) { return __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(v))); }
 
+// kNiT: the importance samples, kNi or kNi64 -- a compile-time shape, as
+// render_fwd_kernel's (the merge network, the fine tile loop, the fine
+// composite's samples per lane; u holds kNiT values).  kNdc: the launch's
+// flag for NDC rays (ImageK::ndc), ndc_ray at the ray's start.
+template <int kNiT, bool kNdc>
 __global__ __launch_bounds__(64 * kImgBlockWaves)
 __attribute__((amdgpu_waves_per_eu(kFwdWavesPerSimd, kFwdWavesPerSimd)))
 void render_image_kernel(ImageK k) {
+  constexpr int kSfT = kSc + kNiT;   // the ray's fine samples
   __shared__ __attribute__((aligned(16))) float smem[kImgBlockWaves * kFLds + kGsLds + kImgPixLds];
   __shared__ __attribute__((aligned(16))) float fring[kImgBlockWaves][768];
   const int wave = __builtin_amdgcn_readfirstlane((int)threadIdx.x >> 6);
@@ -123,6 +134,7 @@ void render_image_kernel(ImageK k) {
     x.fx = k.fx; x.fy = k.fy; x.cx = k.cx; x.cy = k.cy; x.near = k.near; x.far = k.far;
     x.H = k.H; x.W = k.W; x.pose_stride = k.pose_stride; x.variant = k.variant;
     x.Hb = k.Hb; x.Wb = k.Wb;
+    x.ndc = k.ndc; x.sx = k.sx; x.sy = k.sy;
     x.poses = k.poses;
     x.rgb = k.rgb; x.depth = k.depth; x.acc = k.acc; x.rays = k.rays;
     const uint32_t* w = reinterpret_cast<const uint32_t*>(&x);
@@ -191,6 +203,7 @@ void render_image_kernel(ImageK k) {
       }
       float v[11];
       pixel_ray(x.fx, x.fy, x.cx, x.cy, x.near, x.far, x.poses + (size_t)view * x.pose_stride, px, py, v);
+      if constexpr (kNdc) ndc_ray(x.sx, x.sy, v);   // (near, far and the view direction stay the world ray's)
       if (x.rays && lane == 0) {
 #pragma unroll
         for (int a = 0; a < 11; ++a) x.rays[11 * ray + a] = v[a];
@@ -213,14 +226,14 @@ void render_image_kernel(ImageK k) {
     composite_fwd<kSc / 64>(L + kFRaw, L + kFZc, nullptr, kSc, r.dnorm, k.f.white != 0, L + kFW, co, lane);
 
     // ---- importance sampling (:547-551), the det uniforms ----
-    importance_sort(L, k.f.u, srcl, lane);
+    importance_sort<kNiT>(L, k.f.u, srcl, lane);
 
     // ---- fine network (:556); the drain: the slot's tiles are written ----
     pass_start(k.f.Pf, sh8, L, fring[wave], lane, true);
-    pass_tiles<1>(k.f, gsl, fring[wave], L, r, lane, pol);
+    pass_tiles<1, ImageTiles, kSfT>(k.f, gsl, fring[wave], L, r, lane, pol);
     lds_fence_wave();
     CompOut fo;
-    composite_fwd<kSf / 64>(L + kFRaw, L + kFZs, nullptr, kSf, r.dnorm, k.f.white != 0, nullptr, fo, lane);
+    composite_fwd<kSfT / 64>(L + kFRaw, L + kFZs, nullptr, kSfT, r.dnorm, k.f.white != 0, nullptr, fo, lane);
     if (lane == 0) {
       ImagePix x;
       image_pix_load(pixl, x);

@@ -137,6 +137,37 @@ HN_DEV void pixel_ray(float fx, float fy, float cx, float cy, float near, float 
   for (int a = 0; a < 3; ++a) out[8 + a] = d[a] / nrm;
 }
 
+// render()'s NDC step on a packed ray (run_nerf_helpers.py:349 get_ndc_rays(H,
+// W, K[0][0], 1., o, d), ray_util.py:96-142): out[0:6] rewritten, near, far
+// and the view direction (taken from the world direction before this step)
+// left alone.  Every operation below is one separately rounded float32
+// operation in torch's order (the library is built with -ffp-contract=off), so
+// the result is rays.get_ndc_rays' bit for bit.  The near plane is render()'s
+// constant 1.: torch evaluates 2. * near / o_z as reciprocal(o_z) * 2., which
+// is 2 / o_z bit for bit only because doubling is exact -- another plane needs
+// that restated.  sx, sy: the Python scalars -1. / (W / (2. * focal)) and
+// -1. / (H / (2. * focal)), focal = K[0][0] (the reference's quirk: not cx, cy
+// or fy), formed in float64 by the caller and passed as float32.  A ray with
+// d_z = 0 gets whatever non-finite values these operations give.
+HN_DEV void ndc_ray(float sx, float sy, float out[11]) {
+  const float t = -(1.f + out[2]) / out[5];
+  float o[3];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float td = t * out[3 + a];
+    o[a] = out[a] + td;
+  }
+  const float ox_oz = o[0] / o[2], oy_oz = o[1] / o[2];
+  const float o2 = 1.f + 2.f / o[2];
+  const float dx_dz = out[3] / out[5], dy_dz = out[4] / out[5];
+  out[0] = sx * ox_oz;
+  out[1] = sy * oy_oz;
+  out[2] = o2;
+  out[3] = sx * (dx_dz - ox_oz);
+  out[4] = sy * (dy_dz - oy_oz);
+  out[5] = 1.f - o2;
+}
+
 HN_DEV void emit_ray(const hn_ray_sampler& s, const float* __restrict__ image, const float* __restrict__ c2w,
                      uint32_t x, int64_t r, float* __restrict__ rays, float* __restrict__ target) {
   const int py = s.crop_y0 + (int)(x / (uint32_t)s.crop_w);

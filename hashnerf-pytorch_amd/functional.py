@@ -1010,6 +1010,70 @@ def make_render_cfg(grid: L.HnGrid, white_bkgd: bool, lindisp: bool, perturb: bo
     return c
 
 
+def _render_views(name, cfg, H, W, K, poses, near, far, table, ws, ndc, t_vals, u, wsb, weights_packed, return_rays,
+                  variant, out):
+    """The whole-image call behind render_views (name "render_views":
+    hn_render_views, u of cfg.n_importance values) and render_image (name
+    "render_image": hn_render_image(_variant), 64 + 128 and world rays)."""
+    L.require_device(poses, table, t_vals, u, *ws)
+    dev = poses.device
+    views = name == "render_views"
+    if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)):
+        raise ValueError(f"hashnerf_amd.{name}: poses must be [n, 3, 4] or [n, 4, 4], got {tuple(poses.shape)}")
+    poses = poses.contiguous()
+    n = poses.shape[0]
+    ni = int(cfg.n_importance) if views else 128
+    if t_vals is None:
+        from .render import _linspace_cached
+        t_vals = _linspace_cached(64, dev)
+    if u is None:
+        u = torch.linspace(0., 1., ni, device=dev)
+    t_vals, u, table = t_vals.contiguous(), u.contiguous(), table.contiguous()
+    if t_vals.numel() != 64 or u.numel() != ni:
+        raise ValueError(f"hashnerf_amd.{name}: t_vals must hold 64 and u {ni} values")
+    ws = [w.contiguous() for w in ws]
+    H, W = int(H), int(W)
+    if out is None:
+        out = (torch.empty((n, H, W, 3), dtype=torch.float32, device=dev),
+               torch.empty((n, H, W), dtype=torch.float32, device=dev),
+               torch.empty((n, H, W), dtype=torch.float32, device=dev))
+    rgb, depth, acc = out
+    L.require_device(rgb, depth, acc)
+    for t, shape in ((rgb, (n, H, W, 3)), (depth, (n, H, W)), (acc, (n, H, W))):
+        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+            raise ValueError(f"hashnerf_amd.{name}: out tensors must be contiguous {shape} on {dev}")
+    rays = torch.empty((n * H * W, 11), dtype=torch.float32, device=dev) if return_rays else None
+    va = L.HnViewArgs()
+    a = va.image
+    a.n_views, a.H, a.W, a.pose_stride = n, H, W, poses.shape[1] * 4
+    a.fx, a.fy, a.cx, a.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
+    a.near, a.far = float(near), float(far)
+    for k, t in (("poses", poses), ("t_vals", t_vals), ("u", u), ("table", table), ("rgb", rgb), ("depth", depth),
+                 ("acc", acc), ("rays", rays)):
+        setattr(a, k, None if t is None else t.data_ptr())
+    a.coarse = L.make_mlp(ws[:5])
+    a.fine = L.make_mlp(ws[5:])
+    a.weights_packed = 1 if weights_packed else 0
+    lib = L.lib()
+    need = lib.hn_render_views_workspace_bytes(cfg) if views else lib.hn_render_image_workspace_bytes(cfg)
+    wsb, nbytes = _caller_ws(name, wsb, need, dev)
+    t0 = TIMER.begin(name)
+    if views:
+        va.ndc, va.variant = int(bool(ndc)), int(variant)
+        if ndc:
+            # get_ndc_rays' Python scalars (ray_util.py:131-136), float64 here, float32 in the struct
+            focal = float(K[0][0])
+            va.ndc_sx, va.ndc_sy = -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
+        L.check(lib.hn_render_views(cfg, va, L.ptr(wsb), nbytes, L.stream(dev)), name)
+    elif variant:
+        L.check(lib.hn_render_image_variant(cfg, a, int(variant), L.ptr(wsb), nbytes, L.stream(dev)),
+                "render_image_variant")
+    else:
+        L.check(lib.hn_render_image(cfg, a, L.ptr(wsb), nbytes, L.stream(dev)), name)
+    TIMER.end(name, t0)
+    return (rgb, depth, acc, rays) if return_rays else (rgb, depth, acc)
+
+
 def render_image(cfg, H, W, K, poses, near, far, table, ws, t_vals=None, u=None, wsb=None, weights_packed=False,
                  return_rays=False, variant=0, out=None):
     """hn_render_image (run_nerf_helpers.py:310-392 under :395-459): every
@@ -1024,52 +1088,24 @@ def render_image(cfg, H, W, K, poses, near, far, table, ws, t_vals=None, u=None,
     hn_render_image_workspace_bytes; its size does not depend on the images);
     weights_packed: it already holds ws's packed copies.  variant: the
     measured design alternatives (L.IMAGE_VARIANTS' bits; bitwise the same
-    images).  out: (rgb, depth, acc) to write into instead of fresh tensors."""
-    L.require_device(poses, table, t_vals, u, *ws)
-    dev = poses.device
-    if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)):
-        raise ValueError(f"hashnerf_amd.render_image: poses must be [n, 3, 4] or [n, 4, 4], got {tuple(poses.shape)}")
-    poses = poses.contiguous()
-    n = poses.shape[0]
-    if t_vals is None:
-        from .render import _linspace_cached
-        t_vals = _linspace_cached(64, dev)
-    if u is None:
-        u = torch.linspace(0., 1., 128, device=dev)
-    t_vals, u, table = t_vals.contiguous(), u.contiguous(), table.contiguous()
-    if t_vals.numel() != 64 or u.numel() != 128:
-        raise ValueError("hashnerf_amd.render_image: t_vals must hold 64 and u 128 values")
-    ws = [w.contiguous() for w in ws]
-    H, W = int(H), int(W)
-    if out is None:
-        out = (torch.empty((n, H, W, 3), dtype=torch.float32, device=dev),
-               torch.empty((n, H, W), dtype=torch.float32, device=dev),
-               torch.empty((n, H, W), dtype=torch.float32, device=dev))
-    rgb, depth, acc = out
-    L.require_device(rgb, depth, acc)
-    for t, shape in ((rgb, (n, H, W, 3)), (depth, (n, H, W)), (acc, (n, H, W))):
-        if tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
-            raise ValueError(f"hashnerf_amd.render_image: out tensors must be contiguous {shape} on {dev}")
-    rays = torch.empty((n * H * W, 11), dtype=torch.float32, device=dev) if return_rays else None
-    a = L.HnImageArgs()
-    a.n_views, a.H, a.W, a.pose_stride = n, H, W, poses.shape[1] * 4
-    a.fx, a.fy, a.cx, a.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
-    a.near, a.far = float(near), float(far)
-    for k, t in (("poses", poses), ("t_vals", t_vals), ("u", u), ("table", table), ("rgb", rgb), ("depth", depth),
-                 ("acc", acc), ("rays", rays)):
-        setattr(a, k, None if t is None else t.data_ptr())
-    a.coarse = L.make_mlp(ws[:5])
-    a.fine = L.make_mlp(ws[5:])
-    a.weights_packed = 1 if weights_packed else 0
-    wsb, nbytes = _caller_ws("render_image", wsb, L.lib().hn_render_image_workspace_bytes(cfg), dev)
-    t0 = TIMER.begin("render_image")
-    if variant:
-        L.check(L.lib().hn_render_image_variant(cfg, a, int(variant), L.ptr(wsb), nbytes, L.stream(dev)),
-                "render_image_variant")
-    else:
-        L.check(L.lib().hn_render_image(cfg, a, L.ptr(wsb), nbytes, L.stream(dev)), "render_image")
-    TIMER.end("render_image", t0)
-    return (rgb, depth, acc, rays) if return_rays else (rgb, depth, acc)
+    images).  out: (rgb, depth, acc) to write into instead of fresh tensors.
+    64 + 128 samples and world rays only: render_views covers the rest."""
+    return _render_views("render_image", cfg, H, W, K, poses, near, far, table, ws, False, t_vals, u, wsb,
+                         weights_packed, return_rays, variant, out)
+
+
+def render_views(cfg, H, W, K, poses, near, far, table, ws, ndc=False, t_vals=None, u=None, wsb=None,
+                 weights_packed=False, return_rays=False, variant=0, out=None):
+    """hn_render_views: render_image for every configuration the fused forward
+    covers with perturb = 0 and no raw noise -- cfg.n_importance 128 or 64, and
+    with ndc=True render()'s NDC rays (get_ndc_rays(H, W, K[0][0], 1., ...) on
+    the device, bit for bit torch's; near, far and the view directions are the
+    world ray's, as in render()).  Same arguments and returns as render_image;
+    u defaults to linspace(0, 1, cfg.n_importance) on the device and must have
+    that width; with return_rays the rays are the final (NDC) ones; wsb >=
+    hn_render_views_workspace_bytes (the same for both counts)."""
+    return _render_views("render_views", cfg, H, W, K, poses, near, far, table, ws, ndc, t_vals, u, wsb,
+                         weights_packed, return_rays, variant, out)
 
 
 def render_rays_fused(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table,

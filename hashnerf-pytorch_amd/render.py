@@ -295,7 +295,51 @@ def render_image(H, W, K, c2w, **render_kwargs):
     return tuple(t[0] for t in out) if single else out
 
 
-_IMAGE_GROUP = 8    # views per render_image launch of render_path: bounds the output buffers
+def _views_ineligible(kw) -> Optional[str]:
+    """Why render_views cannot render this render() configuration (None: it
+    can): everything the fused forward covers with perturb = 0 and no raw
+    noise -- N_importance 64 or 128, ndc either way."""
+    if not _fusable(np.empty((0, 11)), kw.get("network_fn"), kw.get("network_query_fn"), kw.get("N_samples"),
+                    kw.get("N_importance", 0), kw.get("network_fine")):
+        return ("not the fused HashNeRF configuration (16-level hash grid + SH, two NeRFSmall nets, 64 + 128 or "
+                "64 + 64 samples)")
+    for why, bad in (("perturb != 0", kw.get("perturb", 0.) != 0.),
+                     ("raw_noise_std != 0", kw.get("raw_noise_std", 0.) != 0.),
+                     ("no view directions (use_viewdirs=False)", not kw.get("use_viewdirs", False)),
+                     ("c2w_staticcam", kw.get("c2w_staticcam") is not None),
+                     ("retraw", bool(kw.get("retraw", False)))):
+        if bad:
+            return why
+    return None
+
+
+@torch.no_grad()
+def render_views(H, W, K, c2w, **render_kwargs):
+    """render_image for every configuration _views_ineligible accepts: the
+    fused HashNeRF configuration with N_importance 64 or 128 and ndc either way
+    (render()'s default ndc=True means NDC rays here too: the LLFF
+    configurations' evaluation).  Same arguments, same returns, one launch
+    (functional.render_views).  At 64 the inference forward runs for every
+    table size: no binned backward is needed.  Raises ValueError, naming the
+    reason, for perturb, raw noise, no view directions, c2w_staticcam, retraw
+    or anything but the fused configuration."""
+    why = _views_ineligible(render_kwargs)
+    if why is not None:
+        raise ValueError(f"hashnerf_amd.render_views: not eligible: {why}")
+    c2w = torch.as_tensor(c2w)
+    L.require_device(c2w)
+    single = c2w.dim() == 2
+    poses = (c2w[None] if single else c2w)[:, :3, :4]
+    kw = render_kwargs
+    emb = kw["network_query_fn"].embed_fn
+    cfg = HF.make_render_cfg(emb.grid(), bool(kw.get("white_bkgd", False)), bool(kw.get("lindisp", False)), False,
+                             n_importance=kw["N_importance"])
+    out = HF.render_views(cfg, H, W, K, poses, kw.get("near", 0.), kw.get("far", 1.), emb.table,
+                          kw["network_fn"].weights() + kw["network_fine"].weights(), ndc=bool(kw.get("ndc", True)))
+    return tuple(t[0] for t in out) if single else out
+
+
+_IMAGE_GROUP = 8    # views per render_views launch of render_path: bounds the output buffers
 
 
 @torch.no_grad()
@@ -307,21 +351,22 @@ def render_path(render_poses, hwf, K, chunk, render_kwargs, gt_imgs=None, savedi
     when savedir is given, pickled to test_psnrs_avg{avg:0.2f}.pkl like
     :452-456.  The per-frame matplotlib figures (:435-449) are not written:
     plotting is outside the hot path.
-    image_kernel=True renders the poses through render_image, _IMAGE_GROUP
-    views per launch, where the configuration is eligible for it (the same
-    maps, PSNRs and pickle); where it is not, this is the default path."""
+    image_kernel=True renders the poses through render_views, _IMAGE_GROUP
+    views per launch, where the configuration is eligible for it
+    (_views_ineligible: the LLFF configurations too; the same maps, PSNRs and
+    pickle); where it is not, this is the default path."""
     H, W, focal = hwf
     near, far = render_kwargs["near"], render_kwargs["far"]
     if render_factor != 0:
         H, W, focal = H // render_factor, W // render_factor, focal / render_factor
     rgbs, depths, psnrs = [], [], []
-    use_image = image_kernel and _image_ineligible(render_kwargs) is None
+    use_image = image_kernel and _views_ineligible(render_kwargs) is None
     maps = None
     for i, c2w in enumerate(render_poses):
         if use_image:
             if i % _IMAGE_GROUP == 0:
                 group = torch.stack([torch.as_tensor(p)[:3, :4] for p in render_poses[i:i + _IMAGE_GROUP]], 0)
-                maps = render_image(H, W, K, group, **render_kwargs)
+                maps = render_views(H, W, K, group, **render_kwargs)
             rgb, depth = maps[0][i % _IMAGE_GROUP], maps[1][i % _IMAGE_GROUP]
         else:
             rgb, depth, acc, _ = render(H, W, K, chunk=chunk, c2w=c2w[:3, :4], **render_kwargs)

@@ -30,6 +30,7 @@ extern "C" {
  * must zero-fill the args, as every caller of this ABI does), and the additive
  * entry points hn_sample_pool_ordered, hn_render_image (with its
  * hn_render_image_workspace_bytes and hn_render_image_variant),
+ * hn_render_views (with hn_render_views_workspace_bytes),
  * hn_render_fwd_form and hn_render_fwd_pick. */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
@@ -151,8 +152,9 @@ int32_t hn_sample_pdf(const float* bins, const float* weights, const float* u,
  * hn_render_scatter_mode is not 2 (scatter = 1, T > 22, the box-geometry
  * fallback), hn_render_fwd with feat != NULL and hn_render_bwd return
  * HN_E_SHAPE before any launch; the inference forward (feat == NULL) runs for
- * every T.  The whole-image kernel is 64 + 128 only: hn_render_image(_variant)
- * return HN_E_SHAPE and hn_render_image_workspace_bytes 0 for Ni = 64. */
+ * every T.  The whole-image kernel renders both counts through hn_render_views;
+ * its earlier entry points stay 64 + 128 only: hn_render_image(_variant) return
+ * HN_E_SHAPE and hn_render_image_workspace_bytes 0 for Ni = 64. */
 typedef struct hn_render_cfg {
   hn_grid grid;
   int32_t n_samples;      /* 64 */
@@ -565,6 +567,9 @@ int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
  * view -- so the workspace (both nets' packed weights, and per resident wave
  * the two coarse feature tiles its ray's fine pass reuses) depends on cfg
  * only, not on H, W or n_views.
+ * hn_render_image and hn_render_image_variant take 64 + 128 samples and world
+ * rays only (cfg->n_importance = 64: HN_E_SHAPE); hn_render_views below is the
+ * same host path and the same kernel for every configuration it covers.
  * H, W <= 0, n_views < 0, a pose_stride other than 12 or 16, or more than
  * 2^31 - 1 ray groups (4 rays): HN_E_SHAPE; n_views == 0: HN_OK without a launch. */
 typedef struct hn_image_args {
@@ -574,7 +579,8 @@ typedef struct hn_image_args {
   float near, far;
   const float* poses;             /* device [n_views][3][4] row-major c2w */
   const float* t_vals;            /* device [64]  torch.linspace(0,1,64) */
-  const float* u;                 /* device [128] the det importance uniforms, the same for every ray */
+  const float* u;                 /* device [128] ([cfg->n_importance] for hn_render_views) the det
+                                     importance uniforms, the same for every ray */
   const float* table;
   hn_mlp coarse, fine;
   float* rgb;                     /* [n_views][H][W][3] */
@@ -592,6 +598,40 @@ int32_t hn_render_image(const hn_render_cfg* cfg, const hn_image_args* a, void* 
  * consecutive pixels per workgroup.  0 = hn_render_image. */
 int32_t hn_render_image_variant(const hn_render_cfg* cfg, const hn_image_args* a, int32_t variant,
                                 void* workspace, size_t ws_bytes, void* stream);
+
+/* ---- whole images for every fused configuration (additive under ABI 14) ---
+ * hn_render_image's renderer for cfg->n_importance = 128 or 64 (any other
+ * count: HN_E_SHAPE) and, with ndc = 1, for NDC rays: render(H, W, K,
+ * c2w=pose, ndc=True, use_viewdirs=True), the LLFF configurations' evaluation
+ * (near = 0, far = 1 are the caller's, as for any ray).  Everything said of
+ * hn_render_image holds: the rays, the order, the grid, the outputs bit for
+ * bit hn_render_fwd's on the same rays under the same cfg, the status codes,
+ * every check before any launch.  image.u holds cfg->n_importance values.
+ * ndc = 1: each pixel's ray goes through run_nerf_helpers.py:349
+ * get_ndc_rays(H, W, K[0][0], 1., rays_o, rays_d) (ray_util.py:96-142) on the
+ * device, float32 operation for float32 operation in torch's order: origin and
+ * direction are rewritten, near, far and the view direction (normalised from
+ * the world direction before that step, as render() does) are not; image.rays,
+ * when given, receives these final rays.  The near plane is render()'s constant
+ * 1.  ndc_sx = -1. / (W / (2. * focal)) and ndc_sy = -1. / (H / (2. * focal))
+ * with focal = K[0][0], evaluated in double and rounded to float once (what
+ * torch does with a Python scalar times a float32 tensor; the reference uses
+ * H, W and fx here, not cx, cy or fy).  ndc = 0: both factors are ignored.  A
+ * ray whose world direction has d_z = 0 gets the non-finite values those
+ * operations give, and is then rendered as hn_render_fwd renders such a ray.
+ * variant: hn_render_image_variant's bits, 0 = the shipped design.
+ * ndc outside {0, 1} or a variant outside those bits: HN_E_SHAPE.
+ * hn_render_views_workspace_bytes is the same for both counts and equals
+ * hn_render_image_workspace_bytes of the 128 cfg (0 for a refused cfg). */
+typedef struct hn_view_args {
+  hn_image_args image;            /* u: device [cfg->n_importance] */
+  int32_t ndc;                    /* 0 world rays, 1 NDC rays */
+  float ndc_sx, ndc_sy;
+  int32_t variant;
+} hn_view_args;
+size_t  hn_render_views_workspace_bytes(const hn_render_cfg* cfg);
+int32_t hn_render_views(const hn_render_cfg* cfg, const hn_view_args* a, void* workspace, size_t ws_bytes,
+                        void* stream);
 
 #ifdef __cplusplus
 }
