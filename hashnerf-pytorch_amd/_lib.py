@@ -157,6 +157,8 @@ SIGNATURES = {
     "hn_encode_fwd": (C.c_int32, [C.POINTER(HnGrid), _P, C.c_int64, _P, _P, _P, _P]),
     "hn_encode_bwd": (C.c_int32, [C.POINTER(HnGrid), _P, C.c_int64, _P, _P, _P]),
     "hn_sh_fwd": (C.c_int32, [_P, C.c_int64, _P, _P]),
+    "hn_encode_bwd_input": (C.c_int32, [C.POINTER(HnGrid), _P, C.c_int64, _P, _P, _P, _P]),
+    "hn_sh_bwd": (C.c_int32, [_P, _P, C.c_int64, _P, _P]),
     "hn_mlp_workspace_bytes": (C.c_size_t, []),
     "hn_mlp_fwd": (C.c_int32, [C.POINTER(HnMlp), _P, C.c_int64, _P, _P, C.c_size_t, _P]),
     "hn_mlp_bwd": (C.c_int32, [C.POINTER(HnMlp), _P, _P, C.c_int64, _P, C.POINTER(HnMlpGrad), _P,
@@ -165,6 +167,8 @@ SIGNATURES = {
                                      _P, _P, _P, _P]),
     "hn_composite_bwd": (C.c_int32, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P,
                                      _P, _P, _P, _P]),
+    "hn_composite_bwd_inputs": (C.c_int32, [_P, _P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P, _P,
+                                            _P, _P, _P, _P, _P]),
     "hn_sample_pdf": (C.c_int32, [_P, _P, _P, C.c_int64, C.c_int32, C.c_int32, _P, _P]),
     "hn_tv_fwd": (C.c_int32, [C.POINTER(HnTvArgs), _P, _P]),
     "hn_tv_bwd": (C.c_int32, [C.POINTER(HnTvArgs), _P, _P, _P]),

@@ -1,4 +1,5 @@
-// hn_composite.hip -- standalone raw2outputs fwd/bwd (run_nerf_helpers.py:577-628)
+// hn_composite.hip -- standalone raw2outputs fwd/bwd (run_nerf_helpers.py:577-628;
+// the backward w.r.t. raw, and w.r.t. z and rays_d in a kernel of its own)
 // and sample_pdf (run_nerf_helpers.py:264-307): one wave64 per ray.
 #include "hn_render.h"
 
@@ -29,6 +30,21 @@ __global__ __launch_bounds__(256) void composite_fwd_kernel(
   }
 }
 
+// One ray's upstream gradients; a null array = that output has no gradient.
+HN_DEV void load_comp_grad(CompGrad& g, int64_t ray, const float* g_rgb, const float* g_acc, const float* g_depth,
+                           const float* g_entropy) {
+  g.has_rgb = g_rgb != nullptr;
+  g.has_acc = g_acc != nullptr;
+  g.has_depth = g_depth != nullptr;
+  g.has_entropy = g_entropy != nullptr;
+  g.rgb[0] = g.has_rgb ? g_rgb[3 * ray] : 0.f;
+  g.rgb[1] = g.has_rgb ? g_rgb[3 * ray + 1] : 0.f;
+  g.rgb[2] = g.has_rgb ? g_rgb[3 * ray + 2] : 0.f;
+  g.acc = g.has_acc ? g_acc[ray] : 0.f;
+  g.depth = g.has_depth ? g_depth[ray] : 0.f;
+  g.entropy = g.has_entropy ? g_entropy[ray] : 0.f;
+}
+
 template <int N>
 __global__ __launch_bounds__(256) void composite_bwd_kernel(
     const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d,
@@ -42,19 +58,107 @@ __global__ __launch_bounds__(256) void composite_bwd_kernel(
   const float* d = rays_d + 3 * ray;
   const float dnorm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
   CompGrad g;
-  g.has_rgb = g_rgb != nullptr;
-  g.has_acc = g_acc != nullptr;
-  g.has_depth = g_depth != nullptr;
-  g.has_entropy = g_entropy != nullptr;
-  g.rgb[0] = g.has_rgb ? g_rgb[3 * ray] : 0.f;
-  g.rgb[1] = g.has_rgb ? g_rgb[3 * ray + 1] : 0.f;
-  g.rgb[2] = g.has_rgb ? g_rgb[3 * ray + 2] : 0.f;
-  g.acc = g.has_acc ? g_acc[ray] : 0.f;
-  g.depth = g.has_depth ? g_depth[ray] : 0.f;
-  g.entropy = g.has_entropy ? g_entropy[ray] : 0.f;
+  load_comp_grad(g, ray, g_rgb, g_acc, g_depth, g_entropy);
   composite_bwd<N>(raw + ray * S * 4, z + ray * S, noise ? noise + ray * S : nullptr, S, dnorm,
                    white != 0, g, g_weights ? g_weights + ray * S : nullptr, nullptr,
                    d_raw + ray * S * 4, lane);
+}
+
+// Backward w.r.t. z and |d| of one ray.  d loss / d alpha_k is formed exactly
+// as composite_bwd_raw forms it (the same G, suffix sums and dalpha); from
+// there d delta_k = dalpha_k * e_k * sig_k (alpha = 1 - exp(-sig * delta)),
+// delta_k = (z[k+1] - z[k]) * |d|, the last one 1e10 * |d| (:590-593):
+//   d z_j = (d delta_{j-1} - d delta_j) * |d| + w_j * g_depth / acc
+//   d |d| = sum_k d delta_k * dist_k
+// dz (may be null) gets d z; returns d |d|.
+template <int N>
+HN_DEV float composite_bwd_inputs(const CompSamples<N>& cs, const CompTotals& t, const float* z, int S,
+                                  float dnorm, bool white, const CompGrad& g, const float* gw, float* dz,
+                                  int lane) {
+  const float pS = t.qS / t.Q;
+  const float gS = -(ent_logit(pS) + (ent_inside(pS) ? 1.f : 0.f));
+  const float white_term = (g.has_rgb && white) ? -(g.rgb[0] + g.rgb[1] + g.rgb[2]) : 0.f;
+  const float gd_over_a = g.has_depth ? g.depth / t.acc : 0.f;
+  const float gd_num = g.has_depth ? -(g.depth * t.num) / (t.acc * t.acc) : 0.f;
+  float G[N];
+  double Gw[N], Sfx[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    float gk = 0.f;
+    if (cs.valid[k]) {
+      if (g.has_rgb) gk = g.rgb[0] * cs.c[k][0] + g.rgb[1] * cs.c[k][1] + g.rgb[2] * cs.c[k][2] + white_term;
+      if (g.has_acc) gk += g.acc;
+      if (g.has_depth) gk += cs.z[k] * gd_over_a + gd_num;
+      if (g.has_entropy) {
+        const float p = cs.w[k] / t.Q;
+        const float gp = -(ent_logit(p) + (ent_inside(p) ? 1.f : 0.f));
+        gk += g.entropy * ((gp - gS) / t.Q);
+      }
+      if (gw != nullptr) gk += gw[lane * N + k];
+    }
+    G[k] = gk;
+    Gw[k] = (double)(gk * cs.w[k]);
+  }
+  excl_suffix_sum<N>(Gw, Sfx, lane);
+  float dd[N];          // d loss / d dist_k
+  double dn = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    dd[k] = 0.f;
+    if (!cs.valid[k]) continue;
+    const float dalpha = G[k] * cs.T[k] - (float)Sfx[k] / cs.x[k];
+    const float ddelta = dalpha * cs.e[k] * cs.sig[k];
+    const int j = lane * N + k;
+    const float dist = (j + 1 < S) ? z[j + 1] - cs.z[k] : 1e10f;   // composite_samples' dist
+    dn += (double)(ddelta * dist);
+    dd[k] = (j + 1 < S) ? ddelta * dnorm : 0.f;
+  }
+  dn = wave_sum(dn);
+  // d dist of the sample before this lane's first one
+  float prev = shfl_from(dd[N - 1], lane > 0 ? lane - 1 : 0);
+  if (lane == 0) prev = 0.f;
+  if (dz != nullptr) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      if (cs.valid[k]) {
+        float v = prev - dd[k];
+        if (g.has_depth) v += cs.w[k] * gd_over_a;
+        dz[lane * N + k] = v;
+      }
+      prev = dd[k];
+    }
+  }
+  return (float)dn;
+}
+
+template <int N>
+__global__ __launch_bounds__(256) void composite_bwd_inputs_kernel(
+    const float* __restrict__ raw, const float* __restrict__ z, const float* __restrict__ rays_d,
+    const float* __restrict__ noise, int64_t n_rays, int S, int white, const float* __restrict__ g_rgb,
+    const float* __restrict__ g_acc, const float* __restrict__ g_depth,
+    const float* __restrict__ g_entropy, const float* __restrict__ g_weights,
+    float* __restrict__ d_z, float* __restrict__ d_rays_d) {
+  const int lane = threadIdx.x & 63;
+  const int64_t ray = (int64_t)blockIdx.x * kWaves + (threadIdx.x >> 6);
+  if (ray >= n_rays) return;
+  const float* d = rays_d + 3 * ray;
+  const float dnorm = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+  CompGrad g;
+  load_comp_grad(g, ray, g_rgb, g_acc, g_depth, g_entropy);
+  CompSamples<N> cs;
+  composite_samples<N>(raw + ray * S * 4, z + ray * S, noise ? noise + ray * S : nullptr, S, dnorm, cs, lane);
+  CompTotals t;
+  composite_totals<N>(cs, t);
+  const float dn = composite_bwd_inputs<N>(cs, t, z + ray * S, S, dnorm, white != 0, g,
+                                           g_weights ? g_weights + ray * S : nullptr,
+                                           d_z ? d_z + ray * S : nullptr, lane);
+  if (d_rays_d != nullptr && lane == 0) {
+    // torch.norm's backward: g * d / |d|, zero where |d| = 0
+    const float s = dnorm > 0.f ? dn / dnorm : 0.f;
+    d_rays_d[3 * ray] = s * d[0];
+    d_rays_d[3 * ray + 1] = s * d[1];
+    d_rays_d[3 * ray + 2] = s * d[2];
+  }
 }
 
 __global__ __launch_bounds__(256) void sample_pdf_kernel(const float* __restrict__ bins,
@@ -108,6 +212,22 @@ extern "C" int32_t hn_composite_bwd(const float* raw, const float* z, const floa
   HN_DISPATCH_N(n_samples, composite_bwd_kernel, grid, dim3(256), 0, (hipStream_t)stream, raw, z,
                 rays_d, noise, n_rays, n_samples, white_bkgd, g_rgb, g_acc, g_depth, g_entropy,
                 g_weights, d_raw);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_composite_bwd_inputs(const float* raw, const float* z, const float* rays_d,
+                                           const float* noise, int64_t n_rays, int32_t n_samples,
+                                           int32_t white_bkgd, const float* g_rgb, const float* g_acc,
+                                           const float* g_depth, const float* g_entropy,
+                                           const float* g_weights, float* d_z, float* d_rays_d,
+                                           void* stream) {
+  if (n_rays < 0 || n_samples < 1 || n_samples > 256) return HN_E_SHAPE;
+  if (n_rays == 0 || (!d_z && !d_rays_d)) return HN_OK;
+  if (!raw || !z || !rays_d) return HN_E_NULL;
+  const dim3 grid((unsigned)((n_rays + kWaves - 1) / kWaves));
+  HN_DISPATCH_N(n_samples, composite_bwd_inputs_kernel, grid, dim3(256), 0, (hipStream_t)stream, raw, z,
+                rays_d, noise, n_rays, n_samples, white_bkgd, g_rgb, g_acc, g_depth, g_entropy,
+                g_weights, d_z, d_rays_d);
   return hip_status(hipGetLastError());
 }
 

@@ -93,57 +93,71 @@ def _caller_ws(who: str, wsb, nbytes: int, dev):
     return wsb, _ws_size(wsb)
 
 
-def _no_input_grad(name, *ts):
-    for t in ts:
-        if t is not None and t.requires_grad and torch.is_grad_enabled():
-            raise NotImplementedError(
-                f"hashnerf_amd.{name}: gradients w.r.t. sample positions/directions are not "
-                "implemented (the reference path never needs them: rays carry no grad)")
-
-
 # --------------------------------------------------------------------------
 # hash encoding (embedding/hash_encoding.py:84-110)
 # --------------------------------------------------------------------------
 class HashEncodeFn(torch.autograd.Function):
+    """Each gradient is launched only where it is needed: d table
+    (hn_encode_bwd into a zeroed table-sized buffer) for a table that requires
+    grad, d x (hn_encode_bwd_input) for points that do -- a frozen field under
+    pose refinement pays for no table gradient."""
+
     @staticmethod
     def forward(ctx, x: torch.Tensor, table: torch.Tensor, grid: L.HnGrid):
         L.require_device(x, table)
-        x = x.contiguous()
+        x, table = x.contiguous(), table.contiguous()
         n = x.shape[0]
         n_feat = grid.n_levels * grid.n_features
         feat = torch.empty((n, n_feat), dtype=torch.float32, device=x.device)
         keep = torch.empty((n,), dtype=torch.uint8, device=x.device)
-        L.check(L.lib().hn_encode_fwd(grid, L.ptr(x), n, L.ptr(table.contiguous()), L.ptr(feat),
+        L.check(L.lib().hn_encode_fwd(grid, L.ptr(x), n, L.ptr(table), L.ptr(feat),
                                       L.ptr(keep), L.stream(x.device)), "encode_fwd")
-        ctx.save_for_backward(x)
+        ctx.save_for_backward(x, table)
         ctx.grid = grid
-        ctx.table_shape = table.shape
         ctx.mark_non_differentiable(keep)
         return feat, keep.bool()
 
     @staticmethod
     def backward(ctx, dfeat, _dkeep):
-        (x,) = ctx.saved_tensors
-        dtable = torch.zeros(ctx.table_shape, dtype=torch.float32, device=x.device)
-        if dfeat is not None:
-            dfeat = dfeat.contiguous()
+        x, table = ctx.saved_tensors
+        dfeat = dfeat.contiguous()
+        dx = dtable = None
+        if ctx.needs_input_grad[0]:
+            dx = torch.empty_like(x)
+            L.check(L.lib().hn_encode_bwd_input(ctx.grid, L.ptr(x), x.shape[0], L.ptr(table), L.ptr(dfeat),
+                                                L.ptr(dx), L.stream(x.device)), "encode_bwd_input")
+        if ctx.needs_input_grad[1]:
+            dtable = torch.zeros_like(table)
             L.check(L.lib().hn_encode_bwd(ctx.grid, L.ptr(x), x.shape[0], L.ptr(dfeat), L.ptr(dtable),
                                           L.stream(x.device)), "encode_bwd")
-        return None, dtable, None
+        return dx, dtable, None
 
 
 def hash_encode(x, table, grid):
-    _no_input_grad("hash_encode", x)
     return HashEncodeFn.apply(x, table, grid)
+
+
+class SHEncodeFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, d: torch.Tensor):
+        out = torch.empty((d.shape[0], 16), dtype=torch.float32, device=d.device)
+        L.check(L.lib().hn_sh_fwd(L.ptr(d), d.shape[0], L.ptr(out), L.stream(d.device)), "sh_fwd")
+        ctx.save_for_backward(d)
+        return out
+
+    @staticmethod
+    def backward(ctx, dout):
+        (d,) = ctx.saved_tensors
+        dd = torch.empty_like(d)
+        L.check(L.lib().hn_sh_bwd(L.ptr(d), L.ptr(dout.contiguous()), d.shape[0], L.ptr(dd),
+                                  L.stream(d.device)), "sh_bwd")
+        return dd
 
 
 def sh_encode(dirs: torch.Tensor) -> torch.Tensor:
     """SHEncoder.forward, degree 4 (embedding/spherical_harmonic.py:65-103)."""
-    _no_input_grad("sh_encode", dirs)
     L.require_device(dirs)
-    d = dirs.reshape(-1, 3).contiguous()
-    out = torch.empty((d.shape[0], 16), dtype=torch.float32, device=d.device)
-    L.check(L.lib().hn_sh_fwd(L.ptr(d), d.shape[0], L.ptr(out), L.stream(d.device)), "sh_fwd")
+    out = SHEncodeFn.apply(dirs.reshape(-1, 3).contiguous())
     return out.reshape(*dirs.shape[:-1], 16)
 
 
@@ -210,12 +224,19 @@ class CompositeFn(torch.autograd.Function):
             g_depth = gd if g_depth is None else g_depth + gd
         B, S = z.shape
         d_raw = torch.empty_like(raw)
+        gs = [L.contig(g) for g in (g_rgb, g_acc, g_depth, g_ent, g_weights)]
         L.check(L.lib().hn_composite_bwd(L.ptr(raw), L.ptr(z), L.ptr(rays_d), L.ptr(noise), B, S,
-                                         int(ctx.white), L.ptr(L.contig(g_rgb)), L.ptr(L.contig(g_acc)),
-                                         L.ptr(L.contig(g_depth)), L.ptr(L.contig(g_ent)),
-                                         L.ptr(L.contig(g_weights)), L.ptr(d_raw), L.stream(raw.device)),
-                "composite_bwd")
-        return d_raw, None, None, None, None
+                                         int(ctx.white), *(L.ptr(g) for g in gs), L.ptr(d_raw),
+                                         L.stream(raw.device)), "composite_bwd")
+        # z and rays_d (pose refinement; rays with grad): a launch of its own, d_raw as before
+        d_z = torch.empty_like(z) if ctx.needs_input_grad[1] else None
+        d_rays_d = torch.empty_like(rays_d) if ctx.needs_input_grad[2] else None
+        if d_z is not None or d_rays_d is not None:
+            L.check(L.lib().hn_composite_bwd_inputs(L.ptr(raw), L.ptr(z), L.ptr(rays_d), L.ptr(noise), B, S,
+                                                    int(ctx.white), *(L.ptr(g) for g in gs), L.ptr(d_z),
+                                                    L.ptr(d_rays_d), L.stream(raw.device)),
+                    "composite_bwd_inputs")
+        return d_raw, d_z, d_rays_d, None, None
 
 
 def sample_pdf(bins: torch.Tensor, weights: torch.Tensor, u: torch.Tensor) -> torch.Tensor:
@@ -1016,6 +1037,9 @@ def _render_views(name, cfg, H, W, K, poses, near, far, table, ws, ndc, t_vals, 
     hn_render_views, u of cfg.n_importance values) and render_image (name
     "render_image": hn_render_image(_variant), 64 + 128 and world rays)."""
     L.require_device(poses, table, t_vals, u, *ws)
+    if torch.is_grad_enabled() and poses.requires_grad:
+        raise ValueError(f"hashnerf_amd.{name}: the whole-image kernel has no gradient w.r.t. the poses; "
+                         "render(H, W, K, c2w=pose) is differentiable in them (or detach the poses)")
     dev = poses.device
     views = name == "render_views"
     if poses.dim() != 3 or tuple(poses.shape[1:]) not in ((3, 4), (4, 4)):

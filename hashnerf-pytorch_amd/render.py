@@ -4,8 +4,10 @@ raw2outputs, sample_pdf, run_network, batchify, render_path) on HIP kernels.
 ``render_rays`` dispatches to the fused forward/backward kernels
 (``functional.RenderRaysFn``) whenever the configuration is the HashNeRF one
 (NetworkQuery over a 16-level HashEmbedder + SH, two NeRFSmall nets, 64+128
-or 64+64 samples with view directions); otherwise it composes the standalone HIP ops
-exactly like the reference composes eager ops.  There is no CPU path.
+or 64+64 samples with view directions) and the rays carry no grad; otherwise it
+composes the standalone HIP ops exactly like the reference composes eager ops,
+differentiable in the rays as well (``render(..., c2w=pose)`` with a pose that
+requires grad).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -123,12 +125,17 @@ def _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, n
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False,
                 lindisp=False, perturb=0., N_importance=0, network_fine=None, white_bkgd=False,
                 raw_noise_std=0., verbose=False, pytest=False):
-    """run_nerf_helpers.py:464-574.  Same arguments, same returned dict."""
+    """run_nerf_helpers.py:464-574.  Same arguments, same returned dict.
+    A ray_batch that requires grad (pose refinement: rays built from a pose
+    with grad) takes the standalone-op composition, which is differentiable
+    in the rays as the reference's eager ops are; the fused kernels form no
+    ray gradient, and before returned none without saying so."""
     L.require_device(ray_batch)
     B = ray_batch.shape[0]
     dev = ray_batch.device
     cfg = None
-    if _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine):
+    ray_grad = ray_batch.requires_grad and torch.is_grad_enabled()
+    if not ray_grad and _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine):
         cfg = HF.make_render_cfg(network_query_fn.embed_fn.grid(), white_bkgd, lindisp, perturb > 0.,
                                  n_importance=N_importance)
         # 64 importance samples (the LLFF configurations): fused on the binned

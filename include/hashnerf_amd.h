@@ -31,7 +31,8 @@ extern "C" {
  * entry points hn_sample_pool_ordered, hn_render_image (with its
  * hn_render_image_workspace_bytes and hn_render_image_variant),
  * hn_render_views (with hn_render_views_workspace_bytes),
- * hn_render_fwd_form and hn_render_fwd_pick. */
+ * hn_render_fwd_form and hn_render_fwd_pick, and the input gradients
+ * hn_encode_bwd_input, hn_sh_bwd and hn_composite_bwd_inputs. */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
 
@@ -104,6 +105,21 @@ int32_t hn_encode_bwd(const hn_grid* g, const float* x, int64_t n, const float* 
 /* SHEncoder.forward, degree 4 (embedding/spherical_harmonic.py:65-103):
  * dirs[n][3] -> out[n][16]. */
 int32_t hn_sh_fwd(const float* dirs, int64_t n, float* out, void* stream);
+/* Gradients with respect to the inputs of the two encodings (additive under
+ * ABI 14): what autograd gives the reference for x.requires_grad_().
+ * hn_encode_bwd_input: autograd of trilinear_interp (hash_encoding.py:130-163)
+ * through w = (x - vmin) / (vmax - vmin) (:143): dx[n][3] (overwritten) =
+ * sum over levels and their two features of dfeat * d f / d w_a / (vmax_a -
+ * vmin_a).  The weights come from the unclamped point and the cell from the
+ * clamped one, as in hn_encode_fwd; nothing flows through floor or the clamp
+ * (:69, :74), so a point outside the box gets the same formula.  No atomics:
+ * dx is bitwise repeatable. */
+int32_t hn_encode_bwd_input(const hn_grid* g, const float* x, int64_t n, const float* table,
+                            const float* dfeat, float* dx, void* stream);
+/* hn_sh_bwd: the derivatives of the 16 polynomials of SHEncoder.forward
+ * (spherical_harmonic.py:65-103): dirs[n][3], dout[n][16] -> ddirs[n][3]
+ * (overwritten). */
+int32_t hn_sh_bwd(const float* dirs, const float* dout, int64_t n, float* ddirs, void* stream);
 
 /* ---- L2 NeRFSmall (MFMA) ------------------------------------------------
  * NeRFSmall.forward (models.py:151-174): x[n][48] = [feat32 | sh16] ->
@@ -131,6 +147,18 @@ int32_t hn_composite_bwd(const float* raw, const float* z, const float* rays_d,
                          int32_t white_bkgd, const float* g_rgb, const float* g_acc,
                          const float* g_depth, const float* g_entropy,
                          const float* g_weights, float* d_raw, void* stream);
+/* Backward w.r.t. z and rays_d (additive under ABI 14; both overwritten,
+ * either may be NULL), from the same inputs and upstream gradients: z through
+ * dists = z[i+1] - z[i] (:590-592) and depth = sum(w z) / sum(w) (:617),
+ * rays_d through dists * ||rays_d|| (:593) -- every other output depends on
+ * them through alpha = 1 - exp(-relu(sigma) * dists) (:596, :607) alone.
+ * d_z[n_rays][S], d_rays_d[n_rays][3]. */
+int32_t hn_composite_bwd_inputs(const float* raw, const float* z, const float* rays_d,
+                                const float* noise, int64_t n_rays, int32_t n_samples,
+                                int32_t white_bkgd, const float* g_rgb, const float* g_acc,
+                                const float* g_depth, const float* g_entropy,
+                                const float* g_weights, float* d_z, float* d_rays_d,
+                                void* stream);
 /* sample_pdf (run_nerf_helpers.py:264-307) with u given:
  * bins[n_rays][nb], weights[n_rays][nb-1], u[n_rays][ns] -> out[n_rays][ns];
  * nb <= 256. */
