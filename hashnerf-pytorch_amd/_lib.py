@@ -113,6 +113,11 @@ class HnUniformDraw(C.Structure):
 UNIFORM_MAX_DRAWS = 4
 
 
+class HnRayNdc(C.Structure):
+    """hn_ray_ndc: a sampler's NDC step (get_ndc_rays' two Python scalars, as float32)."""
+    _fields_ = [("sx", C.c_float), ("sy", C.c_float)]
+
+
 class HnNextBatch(C.Structure):
     """hn_next_batch: hn_sample_batch_morton's arguments, as a job of hn_render_bwd."""
     _fields_ = [("sampler", C.POINTER(HnRaySampler)), ("image", _P), ("c2w", _P), ("n_rays", C.c_int64),
@@ -184,6 +189,17 @@ SIGNATURES = {
     "hn_sample_pool_ordered": (C.c_int32, [C.POINTER(HnRayPool), _P, _P, _P, C.c_int64, C.c_int64,
                                            C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, C.c_uint64,
                                            C.POINTER(HnUniformDraw), C.c_int32, _P]),
+    "hn_sample_rays_ndc": (C.c_int32, [C.POINTER(HnRaySampler), _P, _P, C.c_int64, _P, _P, C.POINTER(HnRayNdc), _P]),
+    "hn_sample_rays_morton_ndc": (C.c_int32, [C.POINTER(HnRaySampler), _P, _P, C.c_int64, _P, _P, _P, C.c_size_t,
+                                              C.POINTER(HnRayNdc), _P]),
+    "hn_sample_batch_morton_ndc": (C.c_int32, [C.POINTER(HnRaySampler), _P, _P, C.c_int64, _P, _P, _P, C.c_size_t,
+                                               C.c_uint64, C.POINTER(HnUniformDraw), C.c_int32,
+                                               C.POINTER(HnRayNdc), _P]),
+    "hn_sample_pool_ndc": (C.c_int32, [C.POINTER(HnRayPool), _P, _P, _P, C.c_int64, C.c_int64, _P, _P,
+                                       C.POINTER(HnRayNdc), _P]),
+    "hn_sample_pool_ordered_ndc": (C.c_int32, [C.POINTER(HnRayPool), _P, _P, _P, C.c_int64, C.c_int64,
+                                               C.POINTER(C.c_float), C.POINTER(C.c_float), _P, _P, _P, C.c_uint64,
+                                               C.POINTER(HnUniformDraw), C.c_int32, C.POINTER(HnRayNdc), _P]),
     "hn_blender_images": (C.c_int32, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P]),
     "hn_loss_fwd": (C.c_int32, [_P, _P, _P, _P, _P, C.c_int64, _P, C.c_int32, C.c_float, C.c_float,
                                 C.c_float, _P, _P]),
@@ -200,6 +216,8 @@ SIGNATURES = {
     "hn_render_fwd_pick": (C.c_int32, [C.c_int64, C.POINTER(C.c_int32)]),
     "hn_render_bwd": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                   C.c_size_t, _P]),
+    "hn_render_bwd_ndc": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P, C.c_size_t,
+                                      C.POINTER(HnRayNdc), _P]),
     "hn_render_image_workspace_bytes": (C.c_size_t, [C.POINTER(HnRenderCfg)]),
     "hn_render_image": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), _P, C.c_size_t, _P]),
     "hn_render_image_variant": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), C.c_int32, _P,

@@ -723,10 +723,12 @@ struct PackK {
 };
 static_assert(kPlaceThreads == kMortonThreads, "morton_emit_block: one thread per Morton index of a tile");
 // next / first: the next batch's pass 2 in the workgroups from `first` on
-// (NextK; first = the placement and repack workgroups)
-__global__ __launch_bounds__(kPlaceThreads) void ovf_place_kernel(BinR k, PackK pk, MortonK next, unsigned first) {
+// (NextK; first = the placement and repack workgroups), ndc = that batch's
+// NDC step (hn_next_batch.ndc): only this pass forms rays
+__global__ __launch_bounds__(kPlaceThreads) void ovf_place_kernel(BinR k, PackK pk, MortonK next, NdcK ndc,
+                                                                  unsigned first) {
   if (blockIdx.x >= first) {
-    morton_emit_block(next, blockIdx.x - first);
+    morton_emit_block(next, ndc, blockIdx.x - first);
     return;
   }
   if (blockIdx.x >= kBwdBlocks) {

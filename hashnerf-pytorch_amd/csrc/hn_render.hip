@@ -665,7 +665,7 @@ static int32_t tv_only_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a
   if ((st = hip_status(hipGetLastError()))) return st;
   const BinR r = owner_args(cfg, a, bins, bg, 0);   // (a->n_rays is 0 here)
   hipLaunchKernelGGL(ovf_place_kernel, dim3(kBwdBlocks), dim3(kPlaceThreads), 0, s, r, PackK{}, MortonK{},
-                     (unsigned)kBwdBlocks);
+                     NdcK{}, (unsigned)kBwdBlocks);
   if ((st = hip_status(hipGetLastError()))) return st;
   launch_owner(r, bg, bg.nbins, s);
   return hip_status(hipGetLastError());
@@ -682,9 +682,11 @@ static void launch_prepass(const B1K& k, hipStream_t s) {
 // scatter into records (+ the TV term's, tv != NULL; + the dW slabs'
 // reduction and the MLP steps), overflow placement (+ the repack), owner pass
 // unless deferred to hn_render_bwd_owner.  nk: the next batch's job (NextK;
-// validated, no workgroups without one) in the lists and placement launches.
+// validated, no workgroups without one) in the lists and placement launches,
+// ndc its NDC step.
 static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a, const BwdPlan& plan, const B1K& k,
-                          const hn_tv_args* tv, const TvK& tvk, NextK& nk, void* workspace, hipStream_t s) {
+                          const hn_tv_args* tv, const TvK& tvk, NextK& nk, const NdcK& ndc, void* workspace,
+                          hipStream_t s) {
   int32_t st;
   // prepass_done: the training forward left d raw and the marks; the lists
   // kernel checks its stamp and takes the pre-pass's side jobs in one extra
@@ -739,7 +741,7 @@ static int32_t bwd_binned(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
   // (+ the next batch's rays: every tile's count is in place since the lists launch)
   const unsigned own = (unsigned)kBwdBlocks + pblocks;
   hipLaunchKernelGGL(ovf_place_kernel, dim3(own + (nk.m.n ? nk.m.blocks : 0u)), dim3(kPlaceThreads), 0, s, r, pk,
-                     nk.m, own);
+                     nk.m, ndc, own);
   if ((st = hip_status(hipGetLastError()))) return st;
   if (!a->owner_defer) {
     launch_owner(r, plan.bg, plan.bg.nbins, s);
@@ -780,16 +782,18 @@ struct BwdCall {
   // TV term: records of the binned scatter (tv_rec), or hn_tv_bwd into d_table (tv_atomic)
   const hn_tv_args *tv_rec = nullptr, *tv_atomic = nullptr;
   NextK nk{};   // the next batch's job (none: no workgroups)
+  NdcK ndc{};   // ... and its NDC step (none: world rays)
 };
 
 // Every check of hn_render_bwd: host work only, so a refused call queues
 // nothing.  (A call with no rays is left to tv_only_bwd's checks.)
 static int32_t check_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* workspace, size_t ws_bytes,
-                         BwdCall& c) {
+                         const hn_ray_ndc* next_ndc, BwdCall& c) {
   int32_t st = check_cfg(cfg);
   if (st) return st;
   if (!a) return HN_E_NULL;
   if (a->n_rays < 0) return HN_E_SHAPE;
+  if (next_ndc && !a->next_batch) return HN_E_SHAPE;   // an NDC step of no job
   // the next batch rides the lists and placement launches of a backward that runs both
   if (a->next_batch && (a->n_rays == 0 || a->owner_defer)) return HN_E_SHAPE;
   if (a->n_rays == 0) return HN_OK;
@@ -810,6 +814,7 @@ static int32_t check_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a, 
     if ((st = make_morton(nb.sampler, nb.image, nb.c2w, nb.n_rays, nb.rays, nb.target, nb.workspace, nb.ws_bytes,
                           c.nk.m)))
       return st;
+    if (c.nk.m.n && (st = make_ndc(next_ndc, c.ndc))) return st;
   }
   if (a->loss) {   // ABI 13: the training loss formed by the pre-pass (hn_render_loss)
     const hn_render_loss& L = *a->loss;
@@ -897,8 +902,13 @@ static B1K fill_b1k(const hn_render_cfg* cfg, const hn_render_bwd_args* a, const
 
 extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                                  void* workspace, size_t ws_bytes, void* stream) {
+  return hn_render_bwd_ndc(cfg, a, workspace, ws_bytes, nullptr, stream);
+}
+
+extern "C" int32_t hn_render_bwd_ndc(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* workspace,
+                                     size_t ws_bytes, const hn_ray_ndc* next_ndc, void* stream) {
   BwdCall c;
-  int32_t st = check_bwd(cfg, a, workspace, ws_bytes, c);
+  int32_t st = check_bwd(cfg, a, workspace, ws_bytes, next_ndc, c);
   if (st) return st;
   hipStream_t s = (hipStream_t)stream;
   if (a->n_rays == 0) return a->tv ? tv_only_bwd(cfg, a, workspace, ws_bytes, s) : HN_OK;
@@ -909,7 +919,7 @@ extern "C" int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_a
   if (!a->weights_packed && (st = mlp_pack2_launch(&a->coarse, ws_at<float>(workspace, L.Pc), &a->fine,
                                                    ws_at<float>(workspace, L.Pf), s)))
     return st;
-  if ((st = c.plan.mode == kModeSplit ? bwd_binned(cfg, a, c.plan, k, c.tv_rec, c.tvk, c.nk, workspace, s)
+  if ((st = c.plan.mode == kModeSplit ? bwd_binned(cfg, a, c.plan, k, c.tv_rec, c.tvk, c.nk, c.ndc, workspace, s)
                                       : bwd_atomic(cfg, a, k, s)))
     return st;
   if (c.tv_atomic) return hn_tv_bwd(c.tv_atomic, a->g_tv, a->d_table, stream);

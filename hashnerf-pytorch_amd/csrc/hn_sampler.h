@@ -168,12 +168,23 @@ HN_DEV void ndc_ray(float sx, float sy, float out[11]) {
   out[5] = 1.f - o2;
 }
 
+// A sampler's NDC step (hn_ray_ndc): a kernel argument of its own beside the
+// draw's, so `on` is wave-uniform (a scalar branch) and the structs of the
+// world-ray draw -- and the kernels that only count, which never form a ray
+// -- stay as they are.  on = 0: world rays.
+struct NdcK {
+  int on;
+  float sx, sy;
+};
+
 HN_DEV void emit_ray(const hn_ray_sampler& s, const float* __restrict__ image, const float* __restrict__ c2w,
-                     uint32_t x, int64_t r, float* __restrict__ rays, float* __restrict__ target) {
+                     const NdcK& ndc, uint32_t x, int64_t r, float* __restrict__ rays,
+                     float* __restrict__ target) {
   const int py = s.crop_y0 + (int)(x / (uint32_t)s.crop_w);
   const int px = s.crop_x0 + (int)(x % (uint32_t)s.crop_w);
   float ray[11];
   pixel_ray(s.fx, s.fy, s.cx, s.cy, s.near, s.far, c2w, px, py, ray);
+  if (ndc.on) ndc_ray(ndc.sx, ndc.sy, ray);
 #pragma unroll
   for (int a = 0; a < 11; ++a) rays[11 * r + a] = ray[a];
   const float* px3 = image + 3 * ((size_t)py * s.W + px);
@@ -184,7 +195,7 @@ HN_DEV void emit_ray(const hn_ray_sampler& s, const float* __restrict__ image, c
 // Pass 2, tile b (after every tile's pass 1: a kernel boundary): the rays of
 // its drawn pixels, behind those of the earlier tiles.  Every thread of a
 // workgroup of exactly kMortonThreads calls it.
-HN_DEV void morton_emit_block(const MortonK& k, unsigned b) {
+HN_DEV void morton_emit_block(const MortonK& k, const NdcK& ndc, unsigned b) {
   __shared__ int part[kMortonThreads / 64 + 1];
   const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
   // rays drawn by the earlier tiles
@@ -207,7 +218,7 @@ HN_DEV void morton_emit_block(const MortonK& k, unsigned b) {
   for (int w = 0; w < wave; ++w) off += part[w];
   if (!sel) return;
   const int64_t r = off + __popcll(bal & ((1ull << lane) - 1ull));
-  emit_ray(k.s, k.image, k.c2w, x, r, k.rays, k.target);
+  emit_ray(k.s, k.image, k.c2w, ndc, x, r, k.rays, k.target);
 }
 
 // ---------------------------------------------------------------------------
@@ -248,6 +259,24 @@ HN_DEV void pool_ray(const hn_ray_pool& p, const float* __restrict__ images, con
   const float* px3 = images + 3 * (((size_t)img * p.H + py) * p.W + px);
 #pragma unroll
   for (int a = 0; a < 3; ++a) tgt[a] = px3[a];
+}
+
+// The ray a pool draw hands out: pool_ray's, then render()'s NDC step where
+// the draw asks for one (the target, near, far and the view direction stay
+// the world ray's)
+HN_DEV void pool_ray_final(const hn_ray_pool& p, const float* __restrict__ images, const float* __restrict__ poses,
+                           const int32_t* __restrict__ ids, int half, const NdcK& ndc, uint32_t q, float r[11],
+                           float t[3]) {
+  pool_ray(p, images, poses, ids, half, q, r, t);
+  if (ndc.on) ndc_ray(ndc.sx, ndc.sy, r);
+}
+// ... written to row `row` of a batch
+HN_DEV void pool_ray_store(const float r[11], const float t[3], size_t row, float* __restrict__ rays,
+                           float* __restrict__ target) {
+#pragma unroll
+  for (int a = 0; a < 11; ++a) rays[11 * row + a] = r[a];
+#pragma unroll
+  for (int a = 0; a < 3; ++a) target[3 * row + a] = t[a];
 }
 
 // One ordered pool draw (hn_sample_pool_ordered)
@@ -301,14 +330,16 @@ HN_DEV uint32_t pool_key(const PoolOrderK& k, const float* r) {
 // array per stage (DESIGN 4.6 has the phase times and what was tried).
 constexpr int kPoolIdxBits = 13;
 static_assert((1 << kPoolIdxBits) == HN_POOL_ORDER_MAX, "key << 13 | i holds every position of a batch");
-HN_DEV void pool_order_block(const PoolOrderK& k) {
+// With an NDC step the key is that of the final (NDC) ray, under the pool's
+// near and far as for a world ray.
+HN_DEV void pool_order_block(const PoolOrderK& k, const NdcK& ndc) {
   __shared__ uint64_t w[HN_POOL_ORDER_MAX];
   const int tid = threadIdx.x;
   for (int i = tid; i < k.padded; i += kMortonThreads) {
     uint64_t word = ~0ull;   // the padding sorts behind every ray
     if (i < k.n) {
       float r[11], t[3];
-      pool_ray(k.p, k.images, k.poses, k.ids, k.half, (uint32_t)(k.start + i), r, t);
+      pool_ray_final(k.p, k.images, k.poses, k.ids, k.half, ndc, (uint32_t)(k.start + i), r, t);
       word = ((uint64_t)pool_key(k, r) << kPoolIdxBits) | (uint64_t)i;
     }
     w[i] = word;
@@ -330,8 +361,9 @@ HN_DEV void pool_order_block(const PoolOrderK& k) {
   for (int j = tid; j < k.n; j += kMortonThreads) {
     const uint64_t word = w[j];
     const uint32_t i = (uint32_t)word & (uint32_t)(HN_POOL_ORDER_MAX - 1);
-    pool_ray(k.p, k.images, k.poses, k.ids, k.half, (uint32_t)(k.start + i), k.rays + 11 * (size_t)j,
-             k.target + 3 * (size_t)j);
+    float r[11], t[3];
+    pool_ray_final(k.p, k.images, k.poses, k.ids, k.half, ndc, (uint32_t)(k.start + i), r, t);
+    pool_ray_store(r, t, (size_t)j, k.rays, k.target);
     if (k.keys) k.keys[j] = (uint32_t)(word >> kPoolIdxBits);
   }
 }
@@ -350,6 +382,16 @@ inline bool morton_geometry(const hn_ray_sampler* s, uint32_t& n_idx, unsigned& 
   n_idx = 1u << (2 * k);
   blocks = (unsigned)((n_idx + kMortonThreads - 1) / kMortonThreads);
   return true;
+}
+
+// A draw's NDC step: none without an hn_ray_ndc; scalars that are not finite
+// or are zero (no focal length gives them) are refused.
+inline int32_t make_ndc(const hn_ray_ndc* n, NdcK& k) {
+  k = NdcK{0, 0.f, 0.f};
+  if (!n) return HN_OK;
+  if (!std::isfinite(n->sx) || !std::isfinite(n->sy) || n->sx == 0.f || n->sy == 0.f) return HN_E_SHAPE;
+  k = NdcK{1, n->sx, n->sy};
+  return HN_OK;
 }
 
 inline int32_t make_uni(uint64_t seed, const hn_uniform_draw* draws, int32_t n_draws, UniK& u) {

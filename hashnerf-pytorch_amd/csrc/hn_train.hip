@@ -20,7 +20,7 @@ namespace hn {
 // ---------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void sample_rays_kernel(hn_ray_sampler s, const float* __restrict__ image,
                                                           const float* __restrict__ c2w, int64_t n,
-                                                          int half, float* __restrict__ rays,
+                                                          int half, NdcK ndc, float* __restrict__ rays,
                                                           float* __restrict__ target) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
@@ -33,6 +33,7 @@ __global__ __launch_bounds__(256) void sample_rays_kernel(hn_ray_sampler s, cons
   const int px = s.crop_x0 + (int)(x % (uint32_t)s.crop_w);
   float ray[11];
   pixel_ray(s.fx, s.fy, s.cx, s.cy, s.near, s.far, c2w, px, py, ray);
+  if (ndc.on) ndc_ray(ndc.sx, ndc.sy, ray);
 #pragma unroll
   for (int a = 0; a < 11; ++a) rays[11 * i + a] = ray[a];
   const float* px3 = image + 3 * ((size_t)py * s.W + px);
@@ -58,7 +59,9 @@ __global__ __launch_bounds__(kMortonThreads) void morton_count_kernel(MortonK k,
     morton_count_block<kMortonThreads>(k, blockIdx.x);
 }
 
-__global__ __launch_bounds__(kMortonThreads) void morton_emit_kernel(MortonK k) { morton_emit_block(k, blockIdx.x); }
+__global__ __launch_bounds__(kMortonThreads) void morton_emit_kernel(MortonK k, NdcK ndc) {
+  morton_emit_block(k, ndc, blockIdx.x);
+}
 
 // ---------------------------------------------------------------------------
 // use_batching ray pool (run_nerf.py:505-521, 544-555).  The reference
@@ -73,21 +76,23 @@ __global__ __launch_bounds__(kMortonThreads) void morton_emit_kernel(MortonK k) 
 __global__ __launch_bounds__(256) void sample_pool_kernel(hn_ray_pool p, const float* __restrict__ images,
                                                           const float* __restrict__ poses,
                                                           const int32_t* __restrict__ ids, int64_t start, int64_t n,
-                                                          int half, float* __restrict__ rays,
+                                                          int half, NdcK ndc, float* __restrict__ rays,
                                                           float* __restrict__ target) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= n) return;
-  pool_ray(p, images, poses, ids, half, (uint32_t)(start + i), rays + 11 * i, target + 3 * i);
+  float r[11], t[3];
+  pool_ray_final(p, images, poses, ids, half, ndc, (uint32_t)(start + i), r, t);
+  pool_ray_store(r, t, (size_t)i, rays, target);
 }
 
 // The batch in Morton order of its rays' mid-depth points (the body in
 // hn_sampler.h): workgroup 0 sorts and emits, the others make the step's
 // uniform draws, as morton_count_kernel places them behind its own.
-__global__ __launch_bounds__(kMortonThreads) void sample_pool_ordered_kernel(PoolOrderK k, UniK u) {
+__global__ __launch_bounds__(kMortonThreads) void sample_pool_ordered_kernel(PoolOrderK k, UniK u, NdcK ndc) {
   if (blockIdx.x >= 1)
     uniform_block<kMortonThreads>(u, blockIdx.x - 1);
   else
-    pool_order_block(k);
+    pool_order_block(k, ndc);
 }
 
 // ---------------------------------------------------------------------------
@@ -199,8 +204,10 @@ __global__ __launch_bounds__(kLossThreads) void loss_fwd_bwd_kernel(
 
 using namespace hn;
 
-extern "C" int32_t hn_sample_rays(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
-                                  float* rays, float* target, void* stream) {
+// Every sampler entry point is its _ndc sibling with no hn_ray_ndc.
+extern "C" int32_t hn_sample_rays_ndc(const hn_ray_sampler* s, const float* image, const float* c2w,
+                                      int64_t n_rays, float* rays, float* target, const hn_ray_ndc* ndc,
+                                      void* stream) {
   if (!s) return HN_E_NULL;
   if (n_rays < 0) return HN_E_SHAPE;
   if (n_rays == 0) return HN_OK;
@@ -210,12 +217,20 @@ extern "C" int32_t hn_sample_rays(const hn_ray_sampler* s, const float* image, c
     return HN_E_SHAPE;
   const uint64_t M = (uint64_t)s->crop_h * (uint64_t)s->crop_w;
   if ((uint64_t)n_rays > M || M > (1ull << 30)) return HN_E_SHAPE;   // without replacement
+  NdcK nk;
+  const int32_t st = make_ndc(ndc, nk);
+  if (st) return st;
   int bits = 2;
   while ((1ull << bits) < M) bits += 2;
   const unsigned blocks = (unsigned)((n_rays + 255) / 256);
   hipLaunchKernelGGL(sample_rays_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *s, image, c2w, n_rays,
-                     bits / 2, rays, target);
+                     bits / 2, nk, rays, target);
   return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_sample_rays(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
+                                  float* rays, float* target, void* stream) {
+  return hn_sample_rays_ndc(s, image, c2w, n_rays, rays, target, nullptr, stream);
 }
 
 extern "C" size_t hn_sample_rays_morton_workspace_bytes(const hn_ray_sampler* s) {
@@ -235,37 +250,51 @@ extern "C" int32_t hn_uniform_philox(uint64_t seed, const hn_uniform_draw* draws
   return hip_status(hipGetLastError());
 }
 
+// The draw's checks, then the NDC step's (an empty draw launches nothing and
+// checks no further, as before)
 static int32_t sample_morton(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
                              float* rays, float* target, void* workspace, size_t ws_bytes, const UniK& u,
-                             hipStream_t stream);
+                             const hn_ray_ndc* ndc, hipStream_t stream) {
+  MortonK k;
+  int32_t st = make_morton(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, k);
+  if (st || k.n == 0) return st;
+  NdcK nk;
+  if ((st = make_ndc(ndc, nk))) return st;
+  hipLaunchKernelGGL(morton_count_kernel, dim3(k.blocks + uni_blocks(u)), dim3(kMortonThreads), 0, stream, k, u);
+  hipLaunchKernelGGL(morton_emit_kernel, dim3(k.blocks), dim3(kMortonThreads), 0, stream, k, nk);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_sample_rays_morton_ndc(const hn_ray_sampler* s, const float* image, const float* c2w,
+                                             int64_t n_rays, float* rays, float* target, void* workspace,
+                                             size_t ws_bytes, const hn_ray_ndc* ndc, void* stream) {
+  UniK u;
+  make_uni(0, nullptr, 0, u);
+  return sample_morton(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, u, ndc, (hipStream_t)stream);
+}
 
 extern "C" int32_t hn_sample_rays_morton(const hn_ray_sampler* s, const float* image, const float* c2w,
                                          int64_t n_rays, float* rays, float* target, void* workspace,
                                          size_t ws_bytes, void* stream) {
+  return hn_sample_rays_morton_ndc(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, nullptr, stream);
+}
+
+extern "C" int32_t hn_sample_batch_morton_ndc(const hn_ray_sampler* s, const float* image, const float* c2w,
+                                              int64_t n_rays, float* rays, float* target, void* workspace,
+                                              size_t ws_bytes, uint64_t seed, const hn_uniform_draw* draws,
+                                              int32_t n_draws, const hn_ray_ndc* ndc, void* stream) {
   UniK u;
-  make_uni(0, nullptr, 0, u);
-  return sample_morton(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, u, (hipStream_t)stream);
+  const int32_t st = make_uni(seed, draws, n_draws, u);
+  if (st) return st;
+  return sample_morton(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, u, ndc, (hipStream_t)stream);
 }
 
 extern "C" int32_t hn_sample_batch_morton(const hn_ray_sampler* s, const float* image, const float* c2w,
                                           int64_t n_rays, float* rays, float* target, void* workspace,
                                           size_t ws_bytes, uint64_t seed, const hn_uniform_draw* draws,
                                           int32_t n_draws, void* stream) {
-  UniK u;
-  const int32_t st = make_uni(seed, draws, n_draws, u);
-  if (st) return st;
-  return sample_morton(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, u, (hipStream_t)stream);
-}
-
-static int32_t sample_morton(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
-                             float* rays, float* target, void* workspace, size_t ws_bytes, const UniK& u,
-                             hipStream_t stream) {
-  MortonK k;
-  const int32_t st = make_morton(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, k);
-  if (st || k.n == 0) return st;
-  hipLaunchKernelGGL(morton_count_kernel, dim3(k.blocks + uni_blocks(u)), dim3(kMortonThreads), 0, stream, k, u);
-  hipLaunchKernelGGL(morton_emit_kernel, dim3(k.blocks), dim3(kMortonThreads), 0, stream, k);
-  return hip_status(hipGetLastError());
+  return hn_sample_batch_morton_ndc(s, image, c2w, n_rays, rays, target, workspace, ws_bytes, seed, draws, n_draws,
+                                    nullptr, stream);
 }
 
 extern "C" int32_t hn_loss_fwd(const float* rgb, const float* rgb0, const float* target, const float* sp,
@@ -308,9 +337,9 @@ extern "C" int32_t hn_loss_fwd_bwd(const float* rgb, const float* rgb0, const fl
   return hip_status(hipGetLastError());
 }
 
-extern "C" int32_t hn_sample_pool(const hn_ray_pool* p, const float* images, const float* poses,
-                                  const int32_t* image_ids, int64_t start, int64_t n_rays, float* rays, float* target,
-                                  void* stream) {
+extern "C" int32_t hn_sample_pool_ndc(const hn_ray_pool* p, const float* images, const float* poses,
+                                      const int32_t* image_ids, int64_t start, int64_t n_rays, float* rays,
+                                      float* target, const hn_ray_ndc* ndc, void* stream) {
   if (!p) return HN_E_NULL;
   if (n_rays < 0 || start < 0) return HN_E_SHAPE;
   if (n_rays == 0) return HN_OK;
@@ -318,19 +347,29 @@ extern "C" int32_t hn_sample_pool(const hn_ray_pool* p, const float* images, con
   if (p->n_images <= 0 || p->H <= 0 || p->W <= 0 || p->pose_stride < 12) return HN_E_SHAPE;
   const uint64_t N = (uint64_t)p->n_images * (uint64_t)p->H * (uint64_t)p->W;
   if (N > (1ull << 30) || (uint64_t)start + (uint64_t)n_rays > N) return HN_E_SHAPE;   // one epoch's positions
+  NdcK nk;
+  const int32_t st = make_ndc(ndc, nk);
+  if (st) return st;
   int bits = 2;
   while ((1ull << bits) < N) bits += 2;
   const unsigned blocks = (unsigned)((n_rays + 255) / 256);
   hipLaunchKernelGGL(sample_pool_kernel, dim3(blocks), dim3(256), 0, (hipStream_t)stream, *p, images, poses,
-                     image_ids, start, n_rays, bits / 2, rays, target);
+                     image_ids, start, n_rays, bits / 2, nk, rays, target);
   return hip_status(hipGetLastError());
 }
 
-extern "C" int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* images, const float* poses,
-                                          const int32_t* image_ids, int64_t start, int64_t n_rays,
-                                          const float* box_min, const float* box_max, float* rays, float* target,
-                                          uint32_t* keys, uint64_t seed, const hn_uniform_draw* draws,
-                                          int32_t n_draws, void* stream) {
+extern "C" int32_t hn_sample_pool(const hn_ray_pool* p, const float* images, const float* poses,
+                                  const int32_t* image_ids, int64_t start, int64_t n_rays, float* rays, float* target,
+                                  void* stream) {
+  return hn_sample_pool_ndc(p, images, poses, image_ids, start, n_rays, rays, target, nullptr, stream);
+}
+
+extern "C" int32_t hn_sample_pool_ordered_ndc(const hn_ray_pool* p, const float* images, const float* poses,
+                                              const int32_t* image_ids, int64_t start, int64_t n_rays,
+                                              const float* box_min, const float* box_max, float* rays,
+                                              float* target, uint32_t* keys, uint64_t seed,
+                                              const hn_uniform_draw* draws, int32_t n_draws,
+                                              const hn_ray_ndc* ndc, void* stream) {
   // hn_sample_pool's checks, in its order
   if (!p) return HN_E_NULL;
   if (n_rays < 0 || start < 0) return HN_E_SHAPE;
@@ -348,8 +387,10 @@ extern "C" int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* ima
     k.box_max[a] = box_max[a];
   }
   UniK u;
-  const int32_t st = make_uni(seed, draws, n_draws, u);
+  int32_t st = make_uni(seed, draws, n_draws, u);
   if (st) return st;
+  NdcK nk;
+  if ((st = make_ndc(ndc, nk))) return st;
   int bits = 2;
   while ((1ull << bits) < N) bits += 2;
   k.p = *p;
@@ -365,8 +406,17 @@ extern "C" int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* ima
   k.target = target;
   k.keys = keys;
   hipLaunchKernelGGL(sample_pool_ordered_kernel, dim3(1 + uni_blocks(u)), dim3(kMortonThreads), 0,
-                     (hipStream_t)stream, k, u);
+                     (hipStream_t)stream, k, u, nk);
   return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* images, const float* poses,
+                                          const int32_t* image_ids, int64_t start, int64_t n_rays,
+                                          const float* box_min, const float* box_max, float* rays, float* target,
+                                          uint32_t* keys, uint64_t seed, const hn_uniform_draw* draws,
+                                          int32_t n_draws, void* stream) {
+  return hn_sample_pool_ordered_ndc(p, images, poses, image_ids, start, n_rays, box_min, box_max, rays, target, keys,
+                                    seed, draws, n_draws, nullptr, stream);
 }
 
 extern "C" int32_t hn_blender_images(const uint8_t* rgba, int64_t n_images, int32_t H, int32_t W, int32_t half_res,

@@ -8,6 +8,7 @@ the kernels, mirroring the C ABI contract.
 from __future__ import annotations
 
 import ctypes as C
+import math
 import os
 import weakref
 from typing import Optional, Sequence
@@ -517,7 +518,11 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
         a.prepass_done = 1
         st.prepass_done = None   # the backward clears the forward's stamp
     t0 = TIMER.begin("render_bwd")
-    L.check(L.lib().hn_render_bwd(st.cfg, a, L.ptr(st.wsb), st.nbytes, L.stream(dev)), "render_bwd")
+    if next_batch is not None and next_batch.ndc is not None:
+        L.check(L.lib().hn_render_bwd_ndc(st.cfg, a, L.ptr(st.wsb), st.nbytes, next_batch.ndc, L.stream(dev)),
+                "render_bwd_ndc")
+    else:
+        L.check(L.lib().hn_render_bwd(st.cfg, a, L.ptr(st.wsb), st.nbytes, L.stream(dev)), "render_bwd")
     TIMER.end("render_bwd", t0)
     # the deferred owner pass reuses these arguments (and the buffers they point to)
     st.bwd_args = (a, keep, step) if owner_defer else None
@@ -646,6 +651,34 @@ def torch_uniform(shapes, dev):
     return outs
 
 
+def ndc_scalars(H, W, focal):
+    """get_ndc_rays' two Python scalars (ray_util.py:131-136) as float64:
+    -1. / (W / (2. * focal)) and -1. / (H / (2. * focal)), focal = K[0][0] --
+    what _render_views puts into hn_view_args.ndc_sx / ndc_sy."""
+    focal = float(focal)
+    return -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
+
+
+def _ray_ndc(who, ndc):
+    """A sampler's ``ndc`` argument as an hn_ray_ndc: None (world rays: the
+    call as it is without), or (H, W, focal) of render()'s
+    get_ndc_rays(H, W, K[0][0], 1., ...).  Refused here, before any library
+    call: anything but three numbers, a size below 1, a focal length that is
+    not positive and finite."""
+    if ndc is None:
+        return None
+    if isinstance(ndc, (str, bytes)) or not hasattr(ndc, "__len__") or len(ndc) != 3:
+        raise ValueError(f"{who}: ndc must be None or (H, W, focal), got {ndc!r}")
+    H, W, focal = (float(v) for v in ndc)
+    if not (H >= 1 and W >= 1 and math.isfinite(H) and math.isfinite(W)):
+        raise ValueError(f"{who}: ndc image size {ndc[0]!r} x {ndc[1]!r}")
+    if not (focal > 0. and math.isfinite(focal)):
+        raise ValueError(f"{who}: ndc focal length {ndc[2]!r} must be positive and finite")
+    n = L.HnRayNdc()
+    n.sx, n.sy = ndc_scalars(ndc[0], ndc[1], focal)
+    return n
+
+
 def _ray_sampler(who, image, c2w, n_rays, K, near, far, crop, seed, morton=True):
     """What sample_rays and next_batch set up alike: the hn_ray_sampler of one
     image and window, the contiguous image and [3, 4] pose it is used with,
@@ -672,16 +705,17 @@ class NextBatch:
     """sample_rays(order=1, uniforms=...) as a job of render_bwd
     (hn_render_bwd_args.next_batch): ``job`` the hn_next_batch, ``out`` =
     (rays, target, *uniform tensors) that the backward's launches fill."""
-    __slots__ = ("job", "out", "keep")
+    __slots__ = ("job", "out", "keep", "ndc")   # ndc: the job's hn_ray_ndc (hn_render_bwd_ndc), or None
 
 
-def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None):
-    """The host half of sample_rays(image, ..., order=1, uniforms=uniforms):
-    the sampler's arguments, the output tensors and the default generator's
-    philox offsets (advanced as the torch.rand calls would), without the
-    launches.  render_bwd(next_batch=...) of the binned schedule runs the
-    device half inside its own two small launches, bitwise the values
+def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None, ndc=None):
+    """The host half of sample_rays(image, ..., order=1, uniforms=uniforms,
+    ndc=ndc): the sampler's arguments, the output tensors and the default
+    generator's philox offsets (advanced as the torch.rand calls would),
+    without the launches.  render_bwd(next_batch=...) of the binned schedule
+    runs the device half inside its own two small launches, bitwise the values
     sample_rays would return."""
+    nd = _ray_ndc("next_batch", ndc)
     s, image, c2w, rays, target, ws, nb = _ray_sampler("next_batch", image, c2w, n_rays, K, near, far, crop, seed)
     dev = image.device
     useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
@@ -694,11 +728,11 @@ def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None):
     if arr is not None:
         j.draws = arr
     b = NextBatch()
-    b.job, b.out, b.keep = j, (rays, target, *outs), (s, image, c2w, ws, arr)
+    b.job, b.out, b.keep, b.ndc = j, (rays, target, *outs), (s, image, c2w, ws, arr), nd
     return b
 
 
-def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=None):
+def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=None, ndc=None):
     """N_rand distinct pixels of one image (device, no replacement) -> the
     [n, 11] ray batch render() builds and the [n, 3] target colours.
     image [H, W, 3], c2w [3, 4] (or [4, 4]) fp32 on the device; crop =
@@ -709,24 +743,42 @@ def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=
     groups are spatially coherent; order=0 (hn_sample_rays) keeps the draw
     order.  Both are deterministic for a given seed.  uniforms: shapes of
     torch.rand draws to make as well (torch_uniform; with order=1 in the
-    sampler's first launch), returned after rays and target."""
+    sampler's first launch), returned after rays and target.  ndc = (H, W,
+    focal): rays[:, 0:6] are render()'s NDC rays of the drawn pixels
+    (get_ndc_rays(H, W, focal, 1., o, d) bit for bit, formed in the same
+    launch); near, far, the view direction (the world ray's, normalised) and
+    the target are those of the call without."""
+    if order not in (0, 1):
+        raise ValueError(f"sample_rays: order {order!r}")
+    nd = _ray_ndc("sample_rays", ndc)
     s, image, c2w, rays, target, ws, nb = _ray_sampler("sample_rays(order=1)", image, c2w, n_rays, K, near, far,
                                                        crop, seed, morton=order == 1)
     dev = image.device
     if order == 1:
         if uniforms:
             useed, arr, outs = _uniform_draws(uniforms, dev)
-            L.check(L.lib().hn_sample_batch_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
-                                                   L.ptr(target), L.ptr(ws), nb, useed, arr, len(uniforms),
-                                                   L.stream(dev)), "sample_batch_morton")
+            if nd is None:
+                L.check(L.lib().hn_sample_batch_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
+                                                       L.ptr(target), L.ptr(ws), nb, useed, arr, len(uniforms),
+                                                       L.stream(dev)), "sample_batch_morton")
+            else:
+                L.check(L.lib().hn_sample_batch_morton_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
+                                                           L.ptr(target), L.ptr(ws), nb, useed, arr, len(uniforms),
+                                                           nd, L.stream(dev)), "sample_batch_morton_ndc")
             return (rays, target, *outs)
-        L.check(L.lib().hn_sample_rays_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target),
-                                              L.ptr(ws), nb, L.stream(dev)), "sample_rays_morton")
-    elif order == 0:
+        if nd is None:
+            L.check(L.lib().hn_sample_rays_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target),
+                                                  L.ptr(ws), nb, L.stream(dev)), "sample_rays_morton")
+        else:
+            L.check(L.lib().hn_sample_rays_morton_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
+                                                      L.ptr(target), L.ptr(ws), nb, nd, L.stream(dev)),
+                    "sample_rays_morton_ndc")
+    elif nd is None:
         L.check(L.lib().hn_sample_rays(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target),
                                        L.stream(dev)), "sample_rays")
     else:
-        raise ValueError(f"sample_rays: order {order!r}")
+        L.check(L.lib().hn_sample_rays_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target), nd,
+                                           L.stream(dev)), "sample_rays_ndc")
     if uniforms:
         return (rays, target, *torch_uniform(uniforms, dev))
     return rays, target
@@ -736,7 +788,7 @@ POOL_ORDER_MAX = L.POOL_ORDER_MAX
 
 
 def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays, order=0, box=None, uniforms=None,
-                return_keys=False):
+                return_keys=False, ndc=None):
     """use_batching draw (run_nerf.py:505-521, 544-555): pool positions
     [start, start + n_rays) of the epoch whose shuffle key is `seed`, as the
     [n, 11] ray batch and [n, 3] targets (hn_sample_pool).  images [N, H, W, 3]
@@ -747,9 +799,13 @@ def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays, ord
     box = (min, max), the hash grid's box; positions with equal keys keep the
     shuffle's order.  uniforms: shapes of torch.rand draws to make as well
     (with order=1 in the same launch, else torch_uniform), returned after rays
-    and target; return_keys (order=1) appends the rows' int32 keys."""
+    and target; return_keys (order=1) appends the rows' int32 keys.  ndc =
+    (H, W, focal): the rays' NDC step as in sample_rays; order=1 then keys the
+    NDC rays (mid-depth of `near`, `far`: 0.5 for an LLFF pool) in `box`, the
+    NDC box."""
     if order not in (0, 1):
         raise ValueError(f"sample_pool: order {order!r}")
+    nd = _ray_ndc("sample_pool", ndc)
     if order == 0 and return_keys:
         raise ValueError("sample_pool: return_keys needs order=1")
     if order == 1:
@@ -777,12 +833,23 @@ def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays, ord
         bmax = (C.c_float * 3)(*(float(v) for v in box[1]))
         keys = torch.empty((n_rays,), dtype=torch.int32, device=dev) if return_keys else None
         useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
-        L.check(L.lib().hn_sample_pool_ordered(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start), int(n_rays),
-                                               bmin, bmax, L.ptr(rays), L.ptr(target), L.ptr(keys), useed, arr,
-                                               len(outs), L.stream(dev)), "sample_pool_ordered")
+        if nd is None:
+            L.check(L.lib().hn_sample_pool_ordered(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
+                                                   int(n_rays), bmin, bmax, L.ptr(rays), L.ptr(target), L.ptr(keys),
+                                                   useed, arr, len(outs), L.stream(dev)), "sample_pool_ordered")
+        else:
+            L.check(L.lib().hn_sample_pool_ordered_ndc(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
+                                                       int(n_rays), bmin, bmax, L.ptr(rays), L.ptr(target),
+                                                       L.ptr(keys), useed, arr, len(outs), nd, L.stream(dev)),
+                    "sample_pool_ordered_ndc")
         return (rays, target, *outs, keys) if return_keys else (rays, target, *outs)
-    L.check(L.lib().hn_sample_pool(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
-                                   int(n_rays), L.ptr(rays), L.ptr(target), L.stream(dev)), "sample_pool")
+    if nd is None:
+        L.check(L.lib().hn_sample_pool(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
+                                       int(n_rays), L.ptr(rays), L.ptr(target), L.stream(dev)), "sample_pool")
+    else:
+        L.check(L.lib().hn_sample_pool_ndc(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
+                                           int(n_rays), L.ptr(rays), L.ptr(target), nd, L.stream(dev)),
+                "sample_pool_ndc")
     if uniforms:
         return (rays, target, *torch_uniform(uniforms, dev))
     return rays, target

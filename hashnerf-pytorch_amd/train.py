@@ -29,7 +29,7 @@ import torch.distributed as dist
 from . import functional as HF
 from .create import create_nerf
 from .loss import draw_tv_cubes, tv_loss_levels
-from .rays import bbox_for_blender, blender_cameras, blender_intrinsics, get_rays, pose_spherical
+from .rays import bbox_for_blender, bbox_for_llff, blender_cameras, blender_intrinsics, get_rays, pose_spherical
 from .render import img2mse, mse2psnr, render, render_ray_batch
 
 
@@ -443,10 +443,11 @@ def procedural_field(pts):
 
 
 @torch.no_grad()
-def render_procedural(H, W, K, c2w, near=2., far=6., n_samples=384, chunk=8192, white_bkgd=True):
+def render_procedural(H, W, K, c2w, near=2., far=6., n_samples=384, chunk=8192, white_bkgd=True, shift=None):
     """Ground-truth image [H, W, 3] of procedural_field by dense midpoint
     quadrature of the volume-rendering integral (alpha compositing as
-    raw2outputs, white background as blender)."""
+    raw2outputs, white background as blender).  shift: the field moved by this
+    vector (SyntheticLLFF's scene in front of its cameras)."""
     ro, rd = get_rays(H, W, K, c2w[:3, :4])
     ro, rd = ro.reshape(-1, 3), rd.reshape(-1, 3)
     t = near + (far - near) * (torch.arange(n_samples, device=ro.device) + .5) / n_samples
@@ -455,7 +456,7 @@ def render_procedural(H, W, K, c2w, near=2., far=6., n_samples=384, chunk=8192, 
     for i in range(0, ro.shape[0], chunk):
         o, d = ro[i:i + chunk], rd[i:i + chunk]
         pts = o[:, None] + d[:, None] * t[None, :, None]
-        sigma, rgb = procedural_field(pts)
+        sigma, rgb = procedural_field(pts if shift is None else pts - pts.new_tensor(shift))
         alpha = 1. - torch.exp(-sigma * delta * d.norm(dim=-1, keepdim=True))
         trans = torch.cumprod(torch.cat([torch.ones_like(alpha[:, :1]), 1. - alpha + 1e-10], -1), -1)[:, :-1]
         w = alpha * trans
@@ -492,6 +493,68 @@ class SyntheticBlender:
         self.test_poses = torch.stack([pose_spherical(float(t), -45., 4.0) for t in th], 0).to(device) \
             if n_test else None
         self.test_images = torch.stack([render_procedural(H, W, self.K, c) for c in self.test_poses], 0) \
+            if (n_test and scene == "procedural") else None
+
+
+LLFF_SCENE_SHIFT = (0., 0., -3.)   # the procedural chair, centred 3 in front of the cameras' plane
+
+
+def llff_cameras(n, gen, between=False):
+    """n forward-facing camera-to-world matrices [n, 4, 4]: positions on a small
+    grid around the origin (|x| <= 0.3, |y| <= 0.2, z within +-0.05), looking
+    down -z with yaw and pitch of at most 0.05 rad drawn from ``gen`` -- so
+    every pixel ray of a field of view below ~80 degrees has d_z < 0 and meets
+    the NDC near plane z = -1 in front of its camera.  between: the positions
+    half a cell off the grid (held-out views)."""
+    side = max(int(math.ceil(math.sqrt(max(n, 1)))), 1)
+    ang = (torch.rand((n, 2), generator=gen, dtype=torch.float64) - 0.5) * 0.1
+    out = []
+    for k in range(n):
+        gx = ((k % side) + (0.5 if between else 0.)) / max(side - 1, 1) - 0.5
+        gy = ((k // side) + (0.5 if between else 0.)) / max(side - 1, 1) - 0.5
+        if between:
+            gx, gy = gx * (side - 1) / side, gy * (side - 1) / side
+        yaw, pitch = float(ang[k, 0]), float(ang[k, 1])
+        ry = np.array([[math.cos(yaw), 0., math.sin(yaw)], [0., 1., 0.], [-math.sin(yaw), 0., math.cos(yaw)]])
+        rx = np.array([[1., 0., 0.], [0., math.cos(pitch), -math.sin(pitch)], [0., math.sin(pitch), math.cos(pitch)]])
+        c2w = np.eye(4)
+        c2w[:3, :3] = ry @ rx
+        c2w[:3, 3] = (0.6 * gx, 0.4 * gy, 0.05 * ((k % 3) - 1))
+        out.append(torch.tensor(c2w, dtype=torch.float32))
+    return out
+
+
+class SyntheticLLFF:
+    """Forward-facing stand-in for an LLFF scene (fern, horns, ...: not in the
+    image), held in HBM with SyntheticBlender's fields: n training cameras
+    of llff_cameras, K with focal = 0.8 W (fern's 504-pixel width has 407),
+    and what an LLFF run adds: near = 0., far = 1. (run_nerf.py:270 with NDC
+    rays) and bounding_box = bbox_for_llff(poses, [H, W, focal]) (bbox.py:44-75).
+    scene="uniform": targets uniform in [0,1]^3; scene="procedural":
+    procedural_field moved to LLFF_SCENE_SHIFT -- beyond the NDC near plane
+    z = -1 -- rendered by render_procedural between world depths 1 and 5.5 on
+    a black background, plus n_test held-out views between the grid's."""
+
+    def __init__(self, H, W, n, device, seed=0, scene="uniform", n_test=0):
+        self.H, self.W = H, W
+        self.focal = 0.8 * W
+        self.K = np.array([[self.focal, 0, 0.5 * W], [0, self.focal, 0.5 * H], [0, 0, 1]])
+        self.near, self.far = 0., 1.
+        g = torch.Generator(device="cpu").manual_seed(seed)
+        poses = llff_cameras(n, g)
+        self.poses = torch.stack(poses, 0).to(device)
+        self.bounding_box = bbox_for_llff(torch.stack(poses, 0), [H, W, self.focal])
+        view = lambda c: render_procedural(H, W, self.K, c, near=1., far=5.5, white_bkgd=False,
+                                           shift=LLFF_SCENE_SHIFT)
+        if scene == "uniform":
+            self.images = torch.rand((n, H, W, 3), generator=g).to(device)
+        elif scene == "procedural":
+            self.images = torch.stack([view(c) for c in self.poses], 0)
+        else:
+            raise ValueError(f"SyntheticLLFF scene {scene!r}")
+        self.i_train = torch.arange(n)
+        self.test_poses = torch.stack(llff_cameras(n_test, g, between=True), 0).to(device) if n_test else None
+        self.test_images = torch.stack([view(c) for c in self.test_poses], 0) \
             if (n_test and scene == "procedural") else None
 
 
@@ -540,6 +603,12 @@ class Trainer:
         (self.kw_train, self.kw_test, self.start, self.grad_vars,
          self.optimizer) = create_nerf(args, device=self.device)
         self.embed_fn = self.kw_train["embed_fn"]
+        # the rays' bounds are the data's (run_nerf.py:270-271, :281-283; the
+        # blender pair where it names none), and the samplers hand out render()'s
+        # NDC rays where create_nerf left ndc on (dataset_type llff / st3d without
+        # no_ndc): get_ndc_rays(H, W, K[0][0], 1., ...) in the sampler's launch
+        self.near, self.far = float(getattr(data, "near", 2.)), float(getattr(data, "far", 6.))
+        self.ndc = (data.H, data.W, float(data.K[0][0])) if self.kw_train.get("ndc", True) else None
         self.params = list(self.grad_vars) + list(self.embed_fn.parameters())
         self.global_step = self.start
         self.gen = torch.Generator(device=self.device)
@@ -667,13 +736,13 @@ class Trainer:
         hi = self.i_batch + rem * (self.rank + 1) // self.world
         if self.pool_order == 1:
             g = self.embed_fn.grid()
-            out = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, 2., 6.,
+            out = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, self.near, self.far,
                                  _step_seed(self.seed, 0, -1 - self.epoch), lo, hi - lo, order=1,
                                  box=(list(g.box_min), list(g.box_max)),
-                                 uniforms=[(hi - lo, n) for n in uniforms] if uniforms else None)
+                                 uniforms=[(hi - lo, n) for n in uniforms] if uniforms else None, ndc=self.ndc)
         else:
-            out = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, 2., 6.,
-                                 _step_seed(self.seed, 0, -1 - self.epoch), lo, hi - lo)
+            out = HF.sample_pool(d.images, d.poses, self._pool_ids, d.K, self.near, self.far,
+                                 _step_seed(self.seed, 0, -1 - self.epoch), lo, hi - lo, ndc=self.ndc)
             if uniforms:
                 out = (*out, *HF.torch_uniform([(hi - lo, n) for n in uniforms], self.device))
         self.i_batch += gB
@@ -694,9 +763,9 @@ class Trainer:
         a, d = self.args, self.data
         img_i = self._train_image()
         crop = self.crop if i < a.precrop_iters else (0, 0, d.H, d.W)
-        return HF.sample_rays(d.images[img_i], d.poses[img_i], a.N_rand, d.K, 2., 6., crop,
+        return HF.sample_rays(d.images[img_i], d.poses[img_i], a.N_rand, d.K, self.near, self.far, crop,
                               _step_seed(self.seed, self.rank, i), order=self.ray_order,
-                              uniforms=[(a.N_rand, n) for n in uniforms] if uniforms else None)
+                              uniforms=[(a.N_rand, n) for n in uniforms] if uniforms else None, ndc=self.ndc)
 
     def sample_rays(self, i: int):
         """run_nerf.py:576-605 on the device: one image, N_rand pixels."""
@@ -874,9 +943,9 @@ class Trainer:
         a, d, kw = self.args, self.data, self.kw_train
         img_i = self._train_image()
         crop = self.crop if i < a.precrop_iters else (0, 0, d.H, d.W)
-        nb = HF.next_batch(d.images[img_i], d.poses[img_i], a.N_rand, d.K, 2., 6., crop,
+        nb = HF.next_batch(d.images[img_i], d.poses[img_i], a.N_rand, d.K, self.near, self.far, crop,
                            _step_seed(self.seed, self.rank, i),
-                           uniforms=[(a.N_rand, kw["N_samples"]), (a.N_rand, kw["N_importance"])])
+                           uniforms=[(a.N_rand, kw["N_samples"]), (a.N_rand, kw["N_importance"])], ndc=self.ndc)
         rays, target, t_rand, u = nb.out
         return dict(rays=rays, target=target, t_rand=t_rand, u=u, tv=self._draw_tv(i)), nb
 
@@ -1092,7 +1161,7 @@ class Trainer:
             else:
                 batch_rays, target = self.sample_rays(i)
                 rgb, depth, acc, extras = render(self.data.H, self.data.W, self.data.K, chunk=a.chunk,
-                                                 rays=batch_rays, retraw=True, near=2., far=6.,
+                                                 rays=batch_rays, retraw=True, near=self.near, far=self.far,
                                                  **self.kw_train)
                 loss, mse = self.loss_fn(rgb, extras, target, i)
             loss.backward()

@@ -27,7 +27,10 @@ extern "C" {
 /* 14 also covers three additive fields appended at the end of their structs,
  * where zero / NULL keeps the earlier behaviour: hn_render_fwd_args.loss,
  * hn_render_bwd_args.prepass_done and .next_batch (a caller built against the shorter structs
- * must zero-fill the args, as every caller of this ABI does), and the additive
+ * must zero-fill the args, as every caller of this ABI does), the samplers'
+ * NDC step (hn_ray_ndc with hn_sample_rays_ndc, hn_sample_rays_morton_ndc,
+ * hn_sample_batch_morton_ndc, hn_sample_pool_ndc, hn_sample_pool_ordered_ndc
+ * and, for the next-batch job, hn_render_bwd_ndc), and the additive
  * entry points hn_sample_pool_ordered, hn_render_image (with its
  * hn_render_image_workspace_bytes and hn_render_image_variant),
  * hn_render_views (with hn_render_views_workspace_bytes),
@@ -455,6 +458,39 @@ int32_t hn_uniform_philox(uint64_t seed, const hn_uniform_draw* draws, int32_t n
 int32_t hn_sample_batch_morton(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
                                float* rays, float* target, void* workspace, size_t ws_bytes, uint64_t seed,
                                const hn_uniform_draw* draws, int32_t n_draws, void* stream);
+
+/* The samplers' NDC step (additive under ABI 14; the LLFF configurations,
+ * run_nerf.py:270 with render()'s ndc=True): every sampler -- per image, the
+ * next-batch job, the pool -- can hand out render()'s final ray in the launch
+ * that forms the world ray.  The world ray is formed as without; then
+ * get_ndc_rays(H, W, K[0][0], 1., o, d) (ray_util.py:96-142, the near plane
+ * render() passes, run_nerf_helpers.py:349) rewrites rays[i][0:6], float32
+ * operation for float32 operation as torch evaluates it, so those six floats
+ * are torch's bit for bit.  rays[i][6:8] stay the caller's near / far,
+ * rays[i][8:11] the normalised WORLD direction (render() takes viewdirs
+ * before its NDC step, :350) and the target the pixel.
+ *   sx = -1. / (W / (2. * focal)),  sy = -1. / (H / (2. * focal)),  focal = K[0][0]
+ * formed in float64 by the caller and passed as float32 (hn_view_args.ndc_sx /
+ * ndc_sy are the same two).  A scalar that is not finite or is zero:
+ * HN_E_SHAPE, checked behind the call's other checks and before any launch.
+ * A ray with d_z = 0 (parallel to the near plane) gets whatever non-finite
+ * values those float operations give; no sampler looks for one (a non-finite
+ * sample point raises fault bit 32 in the binned render backward).
+ * ndc == NULL in any call below is the call without the suffix, bitwise; the
+ * entry points without the suffix pass NULL. */
+typedef struct hn_ray_ndc {
+  float sx, sy;
+} hn_ray_ndc;
+int32_t hn_sample_rays_ndc(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
+                           float* rays, float* target, const hn_ray_ndc* ndc, void* stream);
+int32_t hn_sample_rays_morton_ndc(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
+                                  float* rays, float* target, void* workspace, size_t ws_bytes,
+                                  const hn_ray_ndc* ndc, void* stream);
+int32_t hn_sample_batch_morton_ndc(const hn_ray_sampler* s, const float* image, const float* c2w, int64_t n_rays,
+                                   float* rays, float* target, void* workspace, size_t ws_bytes, uint64_t seed,
+                                   const hn_uniform_draw* draws, int32_t n_draws, const hn_ray_ndc* ndc,
+                                   void* stream);
+
 /* The same call as a job of hn_render_bwd (hn_render_bwd_args.next_batch): a
  * training loop's next batch depends on nothing its current step computes, so
  * the binned backward runs the sampler's two passes as extra workgroups of its
@@ -478,6 +514,14 @@ typedef struct hn_next_batch {
   const hn_uniform_draw* draws;
   int32_t n_draws;
 } hn_next_batch;
+/* hn_render_bwd whose next-batch job hands out NDC rays (additive under ABI
+ * 14): a->next_batch drawn as hn_sample_batch_morton_ndc(..., next_ndc, .)
+ * draws it, bitwise, next_ndc checked as that call checks it, with its code,
+ * before anything is queued.  hn_next_batch keeps its layout; next_ndc == NULL
+ * is hn_render_bwd, which passes NULL.  next_ndc without a->next_batch:
+ * HN_E_SHAPE.  The backward's own results do not depend on the job. */
+int32_t hn_render_bwd_ndc(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* workspace, size_t ws_bytes,
+                          const hn_ray_ndc* next_ndc, void* stream);
 
 /* use_batching ray pool (run_nerf.py:505-521 builds rays_rgb from every training
  * pixel and shuffles it; :544-555 takes consecutive N_rand slices and reshuffles
@@ -523,6 +567,18 @@ int32_t hn_sample_pool_ordered(const hn_ray_pool* p, const float* images, const 
                                const int32_t* image_ids, int64_t start, int64_t n_rays, const float* box_min,
                                const float* box_max, float* rays, float* target, uint32_t* keys, uint64_t seed,
                                const hn_uniform_draw* draws, int32_t n_draws, void* stream);
+/* The two pool draws with the NDC step (hn_ray_ndc above; NULL = the calls
+ * above, bitwise).  The ordered draw keys the FINAL ray: o and d in the key
+ * formula above are the NDC ones, tm the mid-depth of the pool's near / far (0.5
+ * for an LLFF pool), box the NDC box the hash grid has (bbox.py:44-75). */
+int32_t hn_sample_pool_ndc(const hn_ray_pool* p, const float* images, const float* poses, const int32_t* image_ids,
+                           int64_t start, int64_t n_rays, float* rays, float* target, const hn_ray_ndc* ndc,
+                           void* stream);
+int32_t hn_sample_pool_ordered_ndc(const hn_ray_pool* p, const float* images, const float* poses,
+                                   const int32_t* image_ids, int64_t start, int64_t n_rays, const float* box_min,
+                                   const float* box_max, float* rays, float* target, uint32_t* keys, uint64_t seed,
+                                   const hn_uniform_draw* draws, int32_t n_draws, const hn_ray_ndc* ndc,
+                                   void* stream);
 
 /* Blender image preparation (load/load_blender.py:63, :78-86; run_nerf.py:259-262):
  * rgba: device uint8 [n][H][W][4] (the PNGs) -> out, float32:
