@@ -218,6 +218,8 @@ SIGNATURES = {
                                   C.c_size_t, _P]),
     "hn_render_bwd_ndc": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P, C.c_size_t,
                                       C.POINTER(HnRayNdc), _P]),
+    "hn_render_bwd_rays_workspace_bytes": (C.c_size_t, [C.POINTER(HnRenderCfg), C.c_int64]),
+    "hn_render_bwd_rays": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P, C.c_size_t, _P, _P]),
     "hn_render_image_workspace_bytes": (C.c_size_t, [C.POINTER(HnRenderCfg)]),
     "hn_render_image": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), _P, C.c_size_t, _P]),
     "hn_render_image_variant": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnImageArgs), C.c_int32, _P,

@@ -180,6 +180,51 @@ HN_DEV void trilerp_bwd(float g, const float w[3], float out[8]) {
   }
 }
 
+// d f / d w of trilerp for one feature's 8 corner values, times the upstream
+// g: autograd's nested-lerp derivatives (hash_encoding.py:145-161 backwards:
+// z, then y, then x), added to dw[3].
+HN_DEV void trilerp_bwd_w(float g, const float e[8], const float w[3], float dw[3]) {
+  const float ax = 1.f - w[0], ay = 1.f - w[1];
+  const float c00 = e[0] * ax + e[4] * w[0];
+  const float c01 = e[1] * ax + e[5] * w[0];
+  const float c10 = e[2] * ax + e[6] * w[0];
+  const float c11 = e[3] * ax + e[7] * w[0];
+  const float c0 = c00 * ay + c10 * w[1];
+  const float c1 = c01 * ay + c11 * w[1];
+  const float g0 = g * (1.f - w[2]), g1 = g * w[2];      // d / d c0, d / d c1
+  dw[2] += g * (c1 - c0);
+  dw[1] += g0 * (c10 - c00) + g1 * (c11 - c01);
+  dw[0] += (g0 * ay) * (e[4] - e[0]) + (g1 * ay) * (e[5] - e[1]) +
+           (g0 * w[1]) * (e[6] - e[2]) + (g1 * w[1]) * (e[7] - e[3]);
+}
+
+// One level's share of d loss / d x for one point: voxel_level's cell and
+// weights, the 8 corner rows, both features' d f / d w, over vmax - vmin
+// (d w_a / d x_a = 1 / (vmax_a - vmin_a), hash_encoding.py:143).  row(h) loads
+// the level's table row h as a float2.
+template <typename Row>
+HN_DEV void level_dx(const float xp[3], const float xc[3], const float gs[3], const float bmin[3], uint32_t mask,
+                     float2 gd, Row row, float dx[3]) {
+  Voxel v;
+  uint32_t cell[3];
+  voxel_level_cell(xp, xc, gs, bmin, mask, v, cell);     // voxel_level's ops
+  float e0[8], e1[8];
+#pragma unroll
+  for (int c = 0; c < 8; ++c) {
+    const float2 t = row(v.h[c]);
+    e0[c] = t.x;
+    e1[c] = t.y;
+  }
+  float dw[3] = {0.f, 0.f, 0.f};
+  trilerp_bwd_w(gd.x, e0, v.w, dw);
+  trilerp_bwd_w(gd.y, e1, v.w, dw);
+#pragma unroll
+  for (int a = 0; a < 3; ++a) {
+    const float vmin = (float)(int32_t)cell[a] * gs[a] + bmin[a];   // vmax - vmin as voxel_level forms it
+    dx[a] += dw[a] / ((vmin + gs[a]) - vmin);
+  }
+}
+
 // RAdam per element (radam.py:58-92) in the op forms of torch's CPU kernels
 // (verified bit-exact on the reference's RAdam trace, tests/golden/radam.npz):
 // add_(x, alpha) = fma(alpha, x, self); addcmul_ = fma(value * t1, t2, self);
@@ -264,6 +309,32 @@ HN_DEV void sh16(float x, float y, float z, float o[16]) {
   o[13] = C3_4 * x * (4.f * zz - xx - yy);
   o[14] = C3_5 * z * (xx - yy);
   o[15] = C3_6 * x * (xx - 3.f * yy);
+}
+
+// d sh16 / d (x, y, z) contracted with the upstream go[16].
+HN_DEV void sh16_bwd(float x, float y, float z, const float go[16], float d[3]) {
+  const float C1 = 0.4886025119029199f;
+  const float C2_0 = 1.0925484305920792f, C2_1 = -1.0925484305920792f,
+              C2_2 = 0.31539156525252005f, C2_3 = -1.0925484305920792f,
+              C2_4 = 0.5462742152960396f;
+  const float C3_0 = -0.5900435899266435f, C3_1 = 2.890611442640554f,
+              C3_2 = -0.4570457994644658f, C3_3 = 0.3731763325901154f,
+              C3_4 = -0.4570457994644658f, C3_5 = 1.445305721320277f,
+              C3_6 = -0.5900435899266435f;
+  const float xx = x * x, yy = y * y, zz = z * z;
+  const float xy = x * y, yz = y * z, xz = x * z;
+  const float g4 = C2_0 * go[4], g5 = C2_1 * go[5], g6 = C2_2 * go[6], g7 = C2_3 * go[7], g8 = C2_4 * go[8];
+  const float g9 = C3_0 * go[9], g10 = C3_1 * go[10], g11 = C3_2 * go[11], g12 = C3_3 * go[12],
+              g13 = C3_4 * go[13], g14 = C3_5 * go[14], g15 = C3_6 * go[15];
+  d[0] = -C1 * go[3] + g4 * y - 2.f * g6 * x + g7 * z + 2.f * g8 * x
+         + 6.f * g9 * xy + g10 * yz - 2.f * g11 * xy - 6.f * g12 * xz
+         + g13 * (4.f * zz - 3.f * xx - yy) + 2.f * g14 * xz + 3.f * g15 * (xx - yy);
+  d[1] = -C1 * go[1] + g4 * x + g5 * z - 2.f * g6 * y - 2.f * g8 * y
+         + 3.f * g9 * (xx - yy) + g10 * xz + g11 * (4.f * zz - xx - 3.f * yy) - 6.f * g12 * yz
+         - 2.f * g13 * xy - 2.f * g14 * yz - 6.f * g15 * xy;
+  d[2] = C1 * go[2] + g5 * y + 4.f * g6 * z + g7 * x
+         + g10 * xy + 8.f * g11 * yz + g12 * (6.f * zz - 3.f * xx - 3.f * yy)
+         + 8.f * g13 * xz + g14 * (xx - yy);
 }
 
 // ---------------------------------------------------------------------------

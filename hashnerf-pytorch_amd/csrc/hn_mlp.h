@@ -384,6 +384,11 @@ HN_DEV void wgrad_accum(const float* Tdy, const float* Tx, float* Wacc, int base
 //   shx8  : sh[8h .. 8h+7] of the point (dW_c0 staging)
 //   T     : this wave's 2 transpose buffers; Wacc: the workgroup's dW accumulator
 //   dsh   : if non-null, also return d sh (standalone NeRFSmall backward)
+// (The same GEMM chain -- R_B4, R_B3, R_B2G / R_B2S, R_B1, R_B0 with the ReLU
+// masks between them -- is written out twice more: b1_tile (hn_mlp_bwd.h, on
+// the weight ring, with the dW products) and mlp_bwd_data_tile (hn_bwd_rays.h,
+// the data path alone on saved mask words).  A change of the regions' layout
+// or order is made in all three.)
 HN_DEV void mlp_bwd_tile(const float* __restrict__ P, const f32x16& feat, const float shx8[8],
                          MlpAct& a, const float dy2[2], float dsig, const float rgbg[3], float* T,
                          float* Wacc, f32x16& dfeat, f32x16* dsh, int lane) {

@@ -243,6 +243,73 @@ HN_DEV void composite_bwd(const float* raw, const float* z, const float* noise, 
   composite_bwd_raw<N>(cs, t, white, g, gw, graw, draw, lane);
 }
 
+// Backward w.r.t. z and |d| of one ray.  d loss / d alpha_k is formed exactly
+// as composite_bwd_raw forms it (the same G, suffix sums and dalpha); from
+// there d delta_k = dalpha_k * e_k * sig_k (alpha = 1 - exp(-sig * delta)),
+// delta_k = (z[k+1] - z[k]) * |d|, the last one 1e10 * |d| (:590-593):
+//   d z_j = (d delta_{j-1} - d delta_j) * |d| + w_j * g_depth / acc
+//   d |d| = sum_k d delta_k * dist_k
+// dz (may be null) gets d z; returns d |d|.
+template <int N>
+HN_DEV float composite_bwd_inputs(const CompSamples<N>& cs, const CompTotals& t, const float* z, int S,
+                                  float dnorm, bool white, const CompGrad& g, const float* gw, float* dz,
+                                  int lane) {
+  const float pS = t.qS / t.Q;
+  const float gS = -(ent_logit(pS) + (ent_inside(pS) ? 1.f : 0.f));
+  const float white_term = (g.has_rgb && white) ? -(g.rgb[0] + g.rgb[1] + g.rgb[2]) : 0.f;
+  const float gd_over_a = g.has_depth ? g.depth / t.acc : 0.f;
+  const float gd_num = g.has_depth ? -(g.depth * t.num) / (t.acc * t.acc) : 0.f;
+  float G[N];
+  double Gw[N], Sfx[N];
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    float gk = 0.f;
+    if (cs.valid[k]) {
+      if (g.has_rgb) gk = g.rgb[0] * cs.c[k][0] + g.rgb[1] * cs.c[k][1] + g.rgb[2] * cs.c[k][2] + white_term;
+      if (g.has_acc) gk += g.acc;
+      if (g.has_depth) gk += cs.z[k] * gd_over_a + gd_num;
+      if (g.has_entropy) {
+        const float p = cs.w[k] / t.Q;
+        const float gp = -(ent_logit(p) + (ent_inside(p) ? 1.f : 0.f));
+        gk += g.entropy * ((gp - gS) / t.Q);
+      }
+      if (gw != nullptr) gk += gw[lane * N + k];
+    }
+    G[k] = gk;
+    Gw[k] = (double)(gk * cs.w[k]);
+  }
+  excl_suffix_sum<N>(Gw, Sfx, lane);
+  float dd[N];          // d loss / d dist_k
+  double dn = 0.0;
+#pragma unroll
+  for (int k = 0; k < N; ++k) {
+    dd[k] = 0.f;
+    if (!cs.valid[k]) continue;
+    const float dalpha = G[k] * cs.T[k] - (float)Sfx[k] / cs.x[k];
+    const float ddelta = dalpha * cs.e[k] * cs.sig[k];
+    const int j = lane * N + k;
+    const float dist = (j + 1 < S) ? z[j + 1] - cs.z[k] : 1e10f;   // composite_samples' dist
+    dn += (double)(ddelta * dist);
+    dd[k] = (j + 1 < S) ? ddelta * dnorm : 0.f;
+  }
+  dn = wave_sum(dn);
+  // d dist of the sample before this lane's first one
+  float prev = shfl_from(dd[N - 1], lane > 0 ? lane - 1 : 0);
+  if (lane == 0) prev = 0.f;
+  if (dz != nullptr) {
+#pragma unroll
+    for (int k = 0; k < N; ++k) {
+      if (cs.valid[k]) {
+        float v = prev - dd[k];
+        if (g.has_depth) v += cs.w[k] * gd_over_a;
+        dz[lane * N + k] = v;
+      }
+      prev = dd[k];
+    }
+  }
+  return (float)dn;
+}
+
 // torch.sum over a contiguous fp32 row on the CPU (ATen SumKernel.cpp
 // vectorized_inner_sum: 8-float vectors, row_sum with 4-way ILP, scalar tail,
 // then the 8 vector lanes) restated for n < 512, so that

@@ -11,6 +11,7 @@
 #include "hn_mlp_bwd.h"       // one tile's MLP backward, dW slabs, render_bwd_kernel's declaration
 #include "hn_bwd_binned.h"    // binned schedule: render_bwd_kernel<kSwVmcnt, kModeSplit>, records, owner pass
 #include "hn_bwd_atomic.h"    // float-atomic fused schedule: render_bwd_kernel<CAP, kModeAtomic>
+#include "hn_bwd_rays.h"      // the ray gradient: render_bwd_rays_kernel and its reduction
 
 #include <math.h>
 
@@ -924,4 +925,91 @@ extern "C" int32_t hn_render_bwd_ndc(const hn_render_cfg* cfg, const hn_render_b
     return st;
   if (c.tv_atomic) return hn_tv_bwd(c.tv_atomic, a->g_tv, a->d_table, stream);
   return HN_OK;
+}
+
+// ---- the ray gradient (hn_bwd_rays.h) ----------------------------------------
+// Scratch of hn_render_bwd_rays, offsets in floats: its own packed copies of
+// both nets | d raw [n][256][4] and the marks [n] (the composite pre-pass
+// writes both) | the units' partial sums [n][8][22].  Nothing of it is read
+// after the call, and it shares nothing with a render workspace.
+struct RaysWs {
+  size_t Pc, Pf, draw, marks, part, total;
+};
+static RaysWs rays_ws_layout(int64_t n_rays) {
+  const size_t n = n_rays > 0 ? (size_t)n_rays : 0;
+  WsCursor c;
+  RaysWs w;
+  w.Pc = c.take(G_END);
+  w.Pf = c.take(G_END);
+  w.draw = c.take(n * (kSc + kSf) * 4, 4);
+  w.marks = c.take(n * kMarkB / sizeof(float));
+  w.part = c.take(n * kTilesPerRay * kRayPart);
+  w.total = c.at;
+  return w;
+}
+
+extern "C" size_t hn_render_bwd_rays_workspace_bytes(const hn_render_cfg* cfg, int64_t n_rays) {
+  return check_cfg(cfg) || n_rays < 0 ? 0 : rays_ws_layout(n_rays).total * sizeof(float);
+}
+
+extern "C" int32_t hn_render_bwd_rays(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* scratch,
+                                      size_t bytes, float* d_rays, void* stream) {
+  int32_t st = check_cfg(cfg);
+  if (st) return st;
+  if (!a) return HN_E_NULL;
+  if (a->n_rays < 0) return HN_E_SHAPE;
+  if (a->loss || a->prepass_done) return HN_E_SHAPE;   // the upstream gradients are the g_* arrays
+  if (a->n_rays == 0) return HN_OK;
+  if (!a->rays || !a->table || !mlp_ok(a->coarse) || !mlp_ok(a->fine)) return HN_E_NULL;
+  if (!a->z_coarse || !a->z_fine || !a->raw_c || !a->raw_f || !a->fine_src || !a->feat) return HN_E_NULL;
+  if (!d_rays || !scratch) return HN_E_NULL;
+  const RaysWs L = rays_ws_layout(a->n_rays);
+  if (bytes < L.total * sizeof(float)) return HN_E_WORKSPACE;
+  if ((uint64_t)a->n_rays * kTilesPerRay / kRayWaves > 0x7fffffffull) return HN_E_SHAPE;   // the grid's x extent
+  hipStream_t s = (hipStream_t)stream;
+  float *Pc = ws_at<float>(scratch, L.Pc), *Pf = ws_at<float>(scratch, L.Pf);
+  if ((st = mlp_pack2_launch(&a->coarse, Pc, &a->fine, Pf, s))) return st;
+  // the composite pre-pass, as hn_render_bwd launches it: d raw (and the marks, unused here)
+  B1K b{};
+  b.B = a->n_rays;
+  b.white = cfg->white_bkgd;
+  b.rays = a->rays; b.noise_c = a->noise_c; b.noise_f = a->noise_f;
+  b.z_coarse = a->z_coarse; b.z_fine = a->z_fine; b.raw_c = a->raw_c; b.raw_f = a->raw_f;
+  b.g_rgb = a->g_rgb; b.g_depth = a->g_depth; b.g_acc = a->g_acc; b.g_sparsity = a->g_sparsity;
+  b.g_rgb0 = a->g_rgb0; b.g_depth0 = a->g_depth0; b.g_acc0 = a->g_acc0; b.g_sparsity0 = a->g_sparsity0;
+  b.g_raw_f = a->g_raw_f;
+  b.fine_src = a->fine_src;
+  b.draw = ws_at<float>(scratch, L.draw);
+  b.uflags = ws_at<uint8_t>(scratch, L.marks);
+  b.sf = kSc + cfg->n_importance;
+  launch_prepass(b, s);
+  if ((st = hip_status(hipGetLastError()))) return st;
+  RaysK k{};
+  k.B = a->n_rays;
+  k.sf = b.sf;
+  k.nt = (kSc + b.sf) / 32;
+  k.rays = a->rays;
+  k.Pc = Pc; k.Pf = Pf;
+  k.z_coarse = a->z_coarse; k.z_fine = a->z_fine;
+  k.feat = a->feat;
+  k.draw = b.draw;
+  k.table = a->table;
+  k.g = make_grid_args(cfg->grid);
+  k.part = ws_at<float>(scratch, L.part);
+  const int64_t units = a->n_rays * kTilesPerRay;
+  hipLaunchKernelGGL(render_bwd_rays_kernel, dim3((unsigned)((units + kRayWaves - 1) / kRayWaves)),
+                     dim3(64 * kRayWaves), 0, s, k);
+  if ((st = hip_status(hipGetLastError()))) return st;
+  RaysR r{};
+  r.B = a->n_rays;
+  r.nt = k.nt; r.sf = k.sf; r.white = cfg->white_bkgd;
+  r.rays = a->rays; r.noise_c = a->noise_c; r.noise_f = a->noise_f;
+  r.z_coarse = a->z_coarse; r.z_fine = a->z_fine; r.raw_c = a->raw_c; r.raw_f = a->raw_f;
+  r.g_rgb = a->g_rgb; r.g_depth = a->g_depth; r.g_acc = a->g_acc; r.g_sparsity = a->g_sparsity;
+  r.g_rgb0 = a->g_rgb0; r.g_depth0 = a->g_depth0; r.g_acc0 = a->g_acc0; r.g_sparsity0 = a->g_sparsity0;
+  r.part = k.part;
+  r.d_rays = d_rays;
+  hipLaunchKernelGGL(render_bwd_rays_reduce_kernel, dim3((unsigned)((a->n_rays + kRayWaves - 1) / kRayWaves)),
+                     dim3(64 * kRayWaves), 0, s, r);
+  return hip_status(hipGetLastError());
 }

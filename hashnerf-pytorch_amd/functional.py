@@ -369,6 +369,10 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     return out, st
 
 
+# the upstream gradients a backward takes (hn_render_bwd_args' g_* fields)
+_GRAD_NAMES = ("g_rgb", "g_depth", "g_acc", "g_sparsity", "g_rgb0", "g_depth0", "g_acc0", "g_sparsity0", "g_raw_f")
+
+
 def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = False, table_step=None,
                overwrite_mlp: bool = False, tv=None, table_live=None, owner_defer: bool = False, loss=None,
                mlp_step=None, repack: bool = False, prepass_done: bool = False, next_batch=None):
@@ -446,9 +450,7 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     a.coarse = L.make_mlp(st.ws[:5])
     a.fine = L.make_mlp(st.ws[5:])
     keep = []
-    names = ("g_rgb", "g_depth", "g_acc", "g_sparsity", "g_rgb0", "g_depth0", "g_acc0", "g_sparsity0",
-             "g_raw_f")
-    for k, t in [(n, grads.get(n)) for n in names] + [
+    for k, t in [(n, grads.get(n)) for n in _GRAD_NAMES] + [
             ("rays", st.rays), ("noise_c", st.noise_c), ("noise_f", st.noise_f), ("table", st.table),
             ("z_coarse", st.z_c), ("z_fine", st.z_f), ("raw_c", st.raw_c), ("raw_f", st.raw_f),
             ("d_table", d_table)]:
@@ -572,16 +574,63 @@ def zeros_like_all(ts):
     return out
 
 
+def render_bwd_rays(st: RenderState, grads: dict) -> torch.Tensor:
+    """hn_render_bwd_rays: d loss / d rays [B, 11] of the fused forward that left
+    st, from its saved z values, raw outputs and ReLU masks -- columns 0:3 d o,
+    3:6 d d, 8:11 d viewdir; 6:8 (near, far) are written as zeros: no gradient
+    is formed for them.  grads as render_bwd's (missing = 0).  The importance
+    samples are detached, as in the reference, so no gradient flows through
+    z.  Runs on a scratch of its own: st's workspace is untouched, and
+    render_bwd(st, ...) may run before or after; neither a table gradient nor
+    an MLP-weight gradient is formed here.  Bitwise repeatable."""
+    B = st.rays.shape[0]
+    dev = st.rays.device
+    g_raw_f = grads.get("g_raw_f")
+    if g_raw_f is not None and g_raw_f.numel() != st.raw_f.numel():
+        raise ValueError(f"hashnerf_amd.render_bwd_rays: g_raw_f must be {tuple(st.raw_f.shape)} (the cfg's "
+                         f"n_importance = {_fine_counts(st.cfg)[0]}), got {tuple(g_raw_f.shape)}")
+    a = L.HnRenderBwdArgs()
+    a.n_rays = B
+    a.coarse = L.make_mlp(st.ws[:5])
+    a.fine = L.make_mlp(st.ws[5:])
+    keep = []
+    for k, t in [(n, grads.get(n)) for n in _GRAD_NAMES] + [
+            ("rays", st.rays), ("noise_c", st.noise_c), ("noise_f", st.noise_f), ("table", st.table),
+            ("z_coarse", st.z_c), ("z_fine", st.z_f), ("raw_c", st.raw_c), ("raw_f", st.raw_f)]:
+        L.require_device(t)
+        t = L.contig(t)
+        keep.append(t)
+        setattr(a, k, None if t is None else t.data_ptr())
+    a.fine_src = st.fine_src.data_ptr()
+    a.feat = st.feat.data_ptr()
+    d_rays = torch.empty((B, 11), dtype=torch.float32, device=dev)
+    nbytes = L.lib().hn_render_bwd_rays_workspace_bytes(st.cfg, B)
+    scratch = _ws(nbytes, dev)
+    t0 = TIMER.begin("render_bwd_rays")
+    L.check(L.lib().hn_render_bwd_rays(st.cfg, a, L.ptr(scratch), nbytes, L.ptr(d_rays), L.stream(dev)),
+            "render_bwd_rays")
+    TIMER.end("render_bwd_rays", t0)
+    if CHECK_FAULTS:
+        L.check_device_faults()
+    return d_rays
+
+
 class RenderRaysFn(torch.autograd.Function):
     """Inputs: rays [B,11], t_vals [64], t_rand [B,64]|None, u [B,cfg.n_importance],
     noise_c/noise_f |None, table, 5 coarse + 5 fine NeRFSmall weights.
-    Outputs: rgb, depth, acc, sparsity, rgb0, depth0, acc0, sparsity0, z_std, raw."""
+    Outputs: rgb, depth, acc, sparsity, rgb0, depth0, acc0, sparsity0, z_std, raw.
+    The backward launches only what needs_input_grad asks for: render_bwd (table
+    and weight gradients) where a table or weight requires grad, render_bwd_rays
+    where the rays do and the caller opted in (RenderRaysGradFn) -- a frozen field
+    under pose refinement allocates no table gradient and launches no MLP-weight
+    or scatter work."""
 
     @staticmethod
     def forward(ctx, cfg: L.HnRenderCfg, keep_feat: bool, rays, t_vals, t_rand, u, noise_c, noise_f,
                 table, *ws):
         out, st = render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_feat)
         ctx.st = st
+        ctx.ray_grad = False               # RenderRaysGradFn: the caller opted in to d rays
         ctx.set_materialize_grads(False)   # unused outputs => NULL, not zeros (0*inf)
         ctx.mark_non_differentiable(out["z_std"])
         return (out["rgb"], out["depth"], out["acc"], out["sparsity"], out["rgb0"], out["depth0"],
@@ -593,13 +642,30 @@ class RenderRaysFn(torch.autograd.Function):
         if st is None:
             raise RuntimeError("hashnerf_amd.render_rays: forward ran without keeping features "
                                "(no input required grad)")
-        d_table = torch.zeros_like(st.table)
-        dws = zeros_like_all(st.ws)
-        render_bwd(st, dict(g_rgb=g_rgb, g_depth=g_depth, g_acc=g_acc, g_sparsity=g_sp, g_rgb0=g_rgb0,
-                            g_depth0=g_depth0, g_acc0=g_acc0, g_sparsity0=g_sp0, g_raw_f=g_raw),
-                   d_table, dws)
+        grads = dict(g_rgb=g_rgb, g_depth=g_depth, g_acc=g_acc, g_sparsity=g_sp, g_rgb0=g_rgb0,
+                     g_depth0=g_depth0, g_acc0=g_acc0, g_sparsity0=g_sp0, g_raw_f=g_raw)
+        # inputs: cfg, keep_feat, rays, t_vals, t_rand, u, noise_c, noise_f, table, the ten weights
+        need = ctx.needs_input_grad
+        d_rays = render_bwd_rays(st, grads) if need[2] and ctx.ray_grad else None
+        d_table, dws = None, [None] * len(st.ws)
+        if any(need[8:]):
+            d_table = torch.zeros_like(st.table)
+            dws = zeros_like_all(st.ws)
+            render_bwd(st, grads, d_table, dws)
         ctx.st = None
-        return (None, None, None, None, None, None, None, None, d_table, *dws)
+        return (None, None, d_rays, None, None, None, None, None, d_table, *dws)
+
+
+class RenderRaysGradFn(RenderRaysFn):
+    """RenderRaysFn whose backward also forms d rays (render_bwd_rays) where the
+    rays require grad: render_rays_fused(..., ray_grad=True).  RenderRaysFn
+    itself returns None for the rays and launches nothing for them, as before."""
+
+    @staticmethod
+    def forward(ctx, *args):
+        out = RenderRaysFn.forward(ctx, *args)
+        ctx.ray_grad = True
+        return out
 
 
 # --------------------------------------------------------------------------
@@ -1200,8 +1266,12 @@ def render_views(cfg, H, W, K, poses, near, far, table, ws, ndc=False, t_vals=No
 
 
 def render_rays_fused(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table,
-                      coarse_ws: Sequence[torch.Tensor], fine_ws: Sequence[torch.Tensor]):
-    keep_feat = torch.is_grad_enabled() and any(
-        t.requires_grad for t in (table, *coarse_ws, *fine_ws))
-    return RenderRaysFn.apply(cfg, keep_feat, rays, t_vals, t_rand, u, noise_c, noise_f, table,
+                      coarse_ws: Sequence[torch.Tensor], fine_ws: Sequence[torch.Tensor], ray_grad: bool = False):
+    """ray_grad: the saved state is also kept for rays that require grad and the
+    backward forms d rays (render_bwd_rays, RenderRaysGradFn); without it the
+    state is kept only for a table or weight that requires grad and rays with
+    grad get None and no extra launch, as before."""
+    keep_feat = torch.is_grad_enabled() and (any(t.requires_grad for t in (table, *coarse_ws, *fine_ws))
+                                             or (ray_grad and rays.requires_grad))
+    return (RenderRaysGradFn if ray_grad else RenderRaysFn).apply(cfg, keep_feat, rays, t_vals, t_rand, u, noise_c, noise_f, table,
                               *coarse_ws, *fine_ws)

@@ -7,7 +7,9 @@ raw2outputs, sample_pdf, run_network, batchify, render_path) on HIP kernels.
 or 64+64 samples with view directions) and the rays carry no grad; otherwise it
 composes the standalone HIP ops exactly like the reference composes eager ops,
 differentiable in the rays as well (``render(..., c2w=pose)`` with a pose that
-requires grad).  There is no CPU path.
+requires grad).  ``ray_grad="fused"`` keeps rays with grad on the fused
+kernels too: their backward then forms the ray gradient from the saved state
+(``functional.render_bwd_rays``).  There is no CPU path.
 """
 from __future__ import annotations
 
@@ -122,26 +124,50 @@ def _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, n
             and ray_batch.shape[-1] > 8)
 
 
+def _fused_cfg(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine, white_bkgd, lindisp,
+               perturb):
+    """The one eligibility pass of render_rays -> (cfg, None) where the fused
+    kernels cover the call, else (None, the reason)."""
+    if not _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine):
+        return None, ("not the fused HashNeRF configuration (16-level hash grid + SH, two NeRFSmall nets, 64 + 128 "
+                      "or 64 + 64 samples, view directions)")
+    cfg = HF.make_render_cfg(network_query_fn.embed_fn.grid(), white_bkgd, lindisp, perturb > 0.,
+                             n_importance=N_importance)
+    # 64 importance samples (the LLFF configurations): fused on the binned
+    # backward schedule only; elsewhere the standalone ops, as before
+    if N_importance != 128 and L.lib().hn_render_scatter_mode(cfg, ray_batch.shape[0]) != 2:
+        return None, ("N_importance = 64 keeps a forward's state on the binned backward schedule only "
+                      "(hn_render_scatter_mode != 2 for this table and box)")
+    return cfg, None
+
+
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=None, retraw=False,
                 lindisp=False, perturb=0., N_importance=0, network_fine=None, white_bkgd=False,
-                raw_noise_std=0., verbose=False, pytest=False):
+                raw_noise_std=0., verbose=False, pytest=False, ray_grad=None):
     """run_nerf_helpers.py:464-574.  Same arguments, same returned dict.
     A ray_batch that requires grad (pose refinement: rays built from a pose
     with grad) takes the standalone-op composition, which is differentiable
-    in the rays as the reference's eager ops are; the fused kernels form no
-    ray gradient, and before returned none without saying so."""
+    in the rays as the reference's eager ops are.
+    ray_grad="fused" (opt-in; a render_kwargs dict may carry it through
+    render()): such a batch takes the fused forward instead, its state kept,
+    and the backward forms d ray_batch with functional.render_bwd_rays (near
+    and far, columns 6:8, get zeros) -- and the table's and weights' gradients
+    only where they require grad.  Where the fused forward cannot run (another
+    configuration; N_importance = 64 off the binned schedule) that raises
+    ValueError naming the reason.  Rays without grad are unaffected."""
+    if ray_grad not in (None, "fused"):
+        raise ValueError(f"hashnerf_amd.render_rays: ray_grad must be None or \"fused\", got {ray_grad!r}")
     L.require_device(ray_batch)
     B = ray_batch.shape[0]
     dev = ray_batch.device
     cfg = None
-    ray_grad = ray_batch.requires_grad and torch.is_grad_enabled()
-    if not ray_grad and _fusable(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine):
-        cfg = HF.make_render_cfg(network_query_fn.embed_fn.grid(), white_bkgd, lindisp, perturb > 0.,
-                                 n_importance=N_importance)
-        # 64 importance samples (the LLFF configurations): fused on the binned
-        # backward schedule only; elsewhere the standalone ops, as before
-        if N_importance != 128 and L.lib().hn_render_scatter_mode(cfg, B) != 2:
-            cfg = None
+    rays_need_grad = ray_batch.requires_grad and torch.is_grad_enabled()
+    fused_rays = rays_need_grad and ray_grad == "fused"
+    if not rays_need_grad or fused_rays:
+        cfg, why = _fused_cfg(ray_batch, network_fn, network_query_fn, N_samples, N_importance, network_fine,
+                              white_bkgd, lindisp, perturb)
+        if fused_rays and cfg is None:
+            raise ValueError(f"hashnerf_amd.render_rays: ray_grad=\"fused\" not eligible: {why}")
     if cfg is not None:
         emb = network_query_fn.embed_fn
         t_vals = _linspace_cached(N_samples, dev)
@@ -161,7 +187,7 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, embed_fn=Non
             noise_f = _draw((B, N_samples + N_importance), dev, pytest, rn) * raw_noise_std
         (rgb, depth, acc, sp, rgb0, depth0, acc0, sp0, z_std, raw) = HF.render_rays_fused(
             cfg, ray_batch, t_vals, t_rand, u, noise_c, noise_f, emb.table, network_fn.weights(),
-            network_fine.weights())
+            network_fine.weights(), ray_grad=fused_rays)
         ret = {"rgb_map": rgb, "depth_map": depth, "acc_map": acc, "sparsity_loss": sp}
         if retraw:
             ret["raw"] = raw

@@ -634,6 +634,36 @@ int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus);
 int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
 
+/* ---- the gradient with respect to the rays (additive under ABI 14) --------
+ * d loss / d rays [B][11] of the forward whose saved state `a` holds (pose
+ * refinement: a pose's gradient follows by autograd of get_rays /
+ * get_ndc_rays).  near, far and the sampling draws are constants and the
+ * importance samples detached (run_nerf_helpers.py:546), so per ray
+ *   columns 0:3  d o       = sum_k dx_k
+ *   columns 3:6  d d       = sum_k z_k dx_k + d|d| d / |d|   (0 where |d| = 0)
+ *   columns 6:8  near, far : written as 0 (no gradient is formed for them)
+ *   columns 8:11 d viewdir = J_sh(viewdir)^T sum_k dsh_k
+ * over the 64 coarse points (coarse net) and the fine points (fine net); dx_k
+ * is hn_encode_bwd_input's closed form, d|d| hn_composite_bwd_inputs'.  Read
+ * from `a`: n_rays, rays, noise_c / noise_f, table, both nets, z_coarse,
+ * z_fine, raw_c, raw_f, fine_src, feat (its ReLU mask words) and the g_*
+ * upstream gradients; every d* output, step and job field is ignored, `loss`
+ * and `prepass_done` must be unset (HN_E_SHAPE).  Written: d_rays only (=, not
+ * +=).  `scratch` (hn_render_bwd_rays_workspace_bytes; 0 for a cfg
+ * hn_render_fwd refuses) belongs to this call alone -- the nets are packed
+ * into it whatever weights_packed says -- and may be the caller's for any
+ * other use afterwards; a render workspace is neither read nor written, so
+ * hn_render_bwd of the same state may run before or after.  No float atomic:
+ * bitwise repeatable.  A tile of 32 samples whose d raw are all exact zeros
+ * reads none of the saved state, so a skip_dead_color forward's state is
+ * accepted.  Every check precedes the first launch: NULL a / rays / table /
+ * nets / saved tensors / feat / d_rays / scratch HN_E_NULL, scratch too small
+ * HN_E_WORKSPACE, a cfg hn_render_fwd refuses HN_E_SHAPE; n_rays == 0: HN_OK,
+ * nothing launched. */
+size_t hn_render_bwd_rays_workspace_bytes(const hn_render_cfg* cfg, int64_t n_rays);
+int32_t hn_render_bwd_rays(const hn_render_cfg* cfg, const hn_render_bwd_args* a, void* scratch, size_t bytes,
+                           float* d_rays, void* stream);
+
 /* ---- whole images from poses (additive under ABI 14) ----------------------
  * The evaluation renderer: run_nerf_helpers.py:310-392 render(H, W, K,
  * c2w=pose, ndc=False, use_viewdirs=True) with perturb = 0 and raw_noise_std =
