@@ -94,6 +94,20 @@ def _caller_ws(who: str, wsb, nbytes: int, dev):
     return wsb, _ws_size(wsb)
 
 
+_LINSPACE = {}
+
+
+def _linspace_cached(n, dev):
+    """torch.linspace(0, 1, n) made on the CPU as the reference does (:514),
+    copied to the device once (a per-call pageable copy would stall the
+    host on every training step)."""
+    key = (n, str(dev))
+    t = _LINSPACE.get(key)
+    if t is None:
+        t = _LINSPACE[key] = torch.linspace(0., 1., steps=n).to(dev)
+    return t
+
+
 # --------------------------------------------------------------------------
 # hash encoding (embedding/hash_encoding.py:84-110)
 # --------------------------------------------------------------------------
@@ -261,6 +275,14 @@ class RenderState:
     __slots__ = ("cfg", "rays", "noise_c", "noise_f", "table", "ws", "z_c", "z_f", "raw_c", "raw_f",
                  "fine_src", "feat", "wsb", "nbytes", "bwd_args", "skip_dead", "prepass_done", "__weakref__")
 
+    def __init__(self):
+        self.cfg = self.rays = self.noise_c = self.noise_f = self.table = self.ws = None
+        self.z_c = self.z_f = self.raw_c = self.raw_f = self.fine_src = self.feat = None
+        self.wsb = self.nbytes = None
+        self.bwd_args = None        # a render_bwd(owner_defer=True)'s arguments, for render_bwd_owner
+        self.skip_dead = False      # the forward ran with skip_dead_color
+        self.prepass_done = None    # the loss key of a render_fwd(loss=...) no backward has used yet
+
 
 def _fine_counts(cfg):
     """(importance samples, fine samples per ray) of a render cfg: the widths
@@ -273,6 +295,25 @@ def _fine_counts(cfg):
 # backward into it (render_fwd(loss=...)): one workspace holds one ray batch's
 # d raw, so a later such forward on it invalidates the earlier state's
 _PREPASS_ON_WS = {}
+
+
+def _loss_key(loss):
+    """What a render_bwd(prepass_done=True)'s loss must repeat of the one its
+    forward took (RenderState.prepass_done)."""
+    return L.contig(loss["target"]).data_ptr(), float(loss["world"]), float(loss["sparse_w"])
+
+
+def _render_loss(loss, tensors, scalars):
+    """An hn_render_loss with the named tensor and scalar fields of the dict
+    filled in, and those tensors (contiguous: the struct points at them)."""
+    la = L.HnRenderLoss()
+    ts = [L.contig(loss[k]) for k in tensors]
+    L.require_device(*ts)
+    for k, t in zip(tensors, ts):
+        setattr(la, k, t.data_ptr())
+    for k in scalars:
+        setattr(la, k, float(loss[k]))
+    return la, ts
 
 
 def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_feat, wsb=None,
@@ -340,13 +381,9 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
     if loss is not None:
         if not keep_feat:
             raise ValueError("hashnerf_amd.render_fwd: loss= is for a forward whose backward follows (keep_feat)")
-        target = L.contig(loss["target"])
-        L.require_device(target)
+        la, (target,) = _render_loss(loss, ("target",), ("world", "sparse_w"))
         if tuple(target.shape) != (B, 3):
             raise ValueError(f"hashnerf_amd.render_fwd: loss target must be [{B}, 3]")
-        la = L.HnRenderLoss()
-        la.target = target.data_ptr()
-        la.world, la.sparse_w = float(loss["world"]), float(loss["sparse_w"])
         a.loss = C.pointer(la)
     t0 = TIMER.begin("render_fwd")
     L.check(L.lib().hn_render_fwd_form(cfg, a, form, L.ptr(wsb), nbytes, L.stream(dev)), "render_fwd")
@@ -359,18 +396,40 @@ def render_fwd(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table, ws, keep_f
         st.cfg, st.rays, st.noise_c, st.noise_f, st.table, st.ws = cfg, rays, noise_c, noise_f, table, ws
         st.z_c, st.z_f, st.raw_c, st.raw_f = out["z_coarse"], out["z_fine"], out["raw_c"], out["raw_f"]
         st.fine_src, st.feat, st.wsb, st.nbytes = fine_src, feat, wsb, nbytes
-        st.bwd_args = None
         st.skip_dead = bool(skip_dead_color)
-        # what the backward's loss must repeat (None: no composite backward ran here)
-        st.prepass_done = None if la is None else (target.data_ptr(), float(loss["world"]),
-                                                   float(loss["sparse_w"]))
         if la is not None:
+            st.prepass_done = _loss_key(loss)
             _PREPASS_ON_WS[wsb.data_ptr()] = weakref.ref(st)
     return out, st
 
 
 # the upstream gradients a backward takes (hn_render_bwd_args' g_* fields)
 _GRAD_NAMES = ("g_rgb", "g_depth", "g_acc", "g_sparsity", "g_rgb0", "g_depth0", "g_acc0", "g_sparsity0", "g_raw_f")
+
+
+def _bwd_args(who, st: RenderState, grads: dict):
+    """The hn_render_bwd_args of a saved state and its upstream gradients
+    (missing = NULL) -- nets, g_*, rays, noise, table, z, raw, fine_src, feat
+    -- and the list of the contiguous tensors it points at, which the caller
+    keeps alive until its launch is queued."""
+    g_raw_f = grads.get("g_raw_f")
+    if g_raw_f is not None and g_raw_f.numel() != st.raw_f.numel():
+        raise ValueError(f"hashnerf_amd.{who}: g_raw_f must be {tuple(st.raw_f.shape)} (the cfg's "
+                         f"n_importance = {_fine_counts(st.cfg)[0]}), got {tuple(g_raw_f.shape)}")
+    a = L.HnRenderBwdArgs()
+    a.n_rays = st.rays.shape[0]
+    a.coarse = L.make_mlp(st.ws[:5])
+    a.fine = L.make_mlp(st.ws[5:])
+    keep = []
+    for k, t in [(n, grads.get(n)) for n in _GRAD_NAMES] + [
+            ("rays", st.rays), ("noise_c", st.noise_c), ("noise_f", st.noise_f), ("table", st.table),
+            ("z_coarse", st.z_c), ("z_fine", st.z_f), ("raw_c", st.raw_c), ("raw_f", st.raw_f)]:
+        t = L.contig(t)
+        keep.append(t)
+        setattr(a, k, None if t is None else t.data_ptr())
+    a.fine_src = st.fine_src.data_ptr()
+    a.feat = st.feat.data_ptr()
+    return a, keep
 
 
 def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = False, table_step=None,
@@ -418,13 +477,9 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
     next_batch.out once this call's launches have run."""
     B = st.rays.shape[0]
     dev = st.rays.device
-    g_raw_f = grads.get("g_raw_f")
-    if g_raw_f is not None and g_raw_f.numel() != st.raw_f.numel():
-        raise ValueError(f"hashnerf_amd.render_bwd: g_raw_f must be {tuple(st.raw_f.shape)} (the cfg's "
-                         f"n_importance = {_fine_counts(st.cfg)[0]}), got {tuple(g_raw_f.shape)}")
+    # (these refusals read rays, cfg, wsb, skip_dead and prepass_done only: a bare state gets them too)
     if prepass_done:
-        done = getattr(st, "prepass_done", None)
-        if done is None:
+        if st.prepass_done is None:
             raise ValueError("hashnerf_amd.render_bwd: prepass_done needs a render_fwd(loss=...) of this state "
                              "that no backward has used yet")
         if loss is None:
@@ -433,10 +488,10 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
         if owner is None or owner() is not st:
             raise ValueError("hashnerf_amd.render_bwd: prepass_done, but another render_fwd(loss=...) has used "
                              "this workspace since this state's")
-        if done != (L.contig(loss["target"]).data_ptr(), float(loss["world"]), float(loss["sparse_w"])):
+        if st.prepass_done != _loss_key(loss):
             raise ValueError("hashnerf_amd.render_bwd: prepass_done, but the loss (target, world, sparse_w) "
                              "is not the one the forward took")
-    if getattr(st, "skip_dead", False):
+    if st.skip_dead:
         # only the binned dense_bwd = 0 backward runs lists of the tiles that were stored
         if st.cfg.dense_bwd:
             raise ValueError("hashnerf_amd.render_bwd: the forward ran with skip_dead_color (features of tiles "
@@ -445,22 +500,12 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
             raise ValueError("hashnerf_amd.render_bwd: the forward ran with skip_dead_color (features of tiles "
                              "without density not stored); the float-atomic backward this configuration runs "
                              "(hn_render_scatter_mode != 2) loads every tile")
-    a = L.HnRenderBwdArgs()
-    a.n_rays = B
-    a.coarse = L.make_mlp(st.ws[:5])
-    a.fine = L.make_mlp(st.ws[5:])
-    keep = []
-    for k, t in [(n, grads.get(n)) for n in _GRAD_NAMES] + [
-            ("rays", st.rays), ("noise_c", st.noise_c), ("noise_f", st.noise_f), ("table", st.table),
-            ("z_coarse", st.z_c), ("z_fine", st.z_f), ("raw_c", st.raw_c), ("raw_f", st.raw_f),
-            ("d_table", d_table)]:
-        if t is not None and k == "d_table" and not t.is_contiguous():
+    a, keep = _bwd_args("render_bwd", st, grads)
+    if d_table is not None:
+        if not d_table.is_contiguous():
             raise RuntimeError("hashnerf_amd.render_bwd: d_table must be contiguous")
-        t = L.contig(t)
-        keep.append(t)
-        setattr(a, k, None if t is None else t.data_ptr())
-    a.fine_src = st.fine_src.data_ptr()
-    a.feat = st.feat.data_ptr()
+        a.d_table = d_table.data_ptr()
+        keep.append(d_table)
     a.weights_packed = 1               # same workspace and weights as the forward
     a.d_table_mode = (1 if overwrite else 0) | (2 if overwrite_mlp else 0)
     a.d_coarse = L.make_mlp_grad(dws[:5])
@@ -502,14 +547,10 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
         a.repack = 1 if repack else 0
         keep.append(ms)
     if loss is not None:
-        la = L.HnRenderLoss()
-        ts = [L.contig(loss[k]) for k in ("target", "rgb", "rgb0", "sparsity", "sparsity0")]
-        ltv = loss.get("tv")
-        ltv = L.contig(ltv) if ltv is not None else None
-        L.require_device(*ts, ltv, loss["out"])
-        la.target, la.rgb, la.rgb0, la.sparsity, la.sparsity0 = (t.data_ptr() for t in ts)
+        la, ts = _render_loss(loss, ("target", "rgb", "rgb0", "sparsity", "sparsity0"), ("world", "sparse_w", "tv_w"))
+        ltv = L.contig(loss.get("tv"))
+        L.require_device(ltv, loss["out"])
         la.tv, la.n_tv = (ltv.data_ptr(), ltv.numel()) if ltv is not None else (None, 0)
-        la.world, la.sparse_w, la.tv_w = float(loss["world"]), float(loss["sparse_w"]), float(loss["tv_w"])
         la.out = loss["out"].data_ptr()
         a.loss = C.pointer(la)
         keep += ts + [ltv, la]
@@ -520,11 +561,9 @@ def render_bwd(st: RenderState, grads: dict, d_table, dws, overwrite: bool = Fal
         a.prepass_done = 1
         st.prepass_done = None   # the backward clears the forward's stamp
     t0 = TIMER.begin("render_bwd")
-    if next_batch is not None and next_batch.ndc is not None:
-        L.check(L.lib().hn_render_bwd_ndc(st.cfg, a, L.ptr(st.wsb), st.nbytes, next_batch.ndc, L.stream(dev)),
-                "render_bwd_ndc")
-    else:
-        L.check(L.lib().hn_render_bwd(st.cfg, a, L.ptr(st.wsb), st.nbytes, L.stream(dev)), "render_bwd")
+    next_ndc = None if next_batch is None else next_batch.ndc
+    L.check(L.lib().hn_render_bwd_ndc(st.cfg, a, L.ptr(st.wsb), st.nbytes, next_ndc, L.stream(dev)),
+            _ndc_label("render_bwd", next_ndc))
     TIMER.end("render_bwd", t0)
     # the deferred owner pass reuses these arguments (and the buffers they point to)
     st.bwd_args = (a, keep, step) if owner_defer else None
@@ -554,7 +593,7 @@ def render_bwd_owner(st: RenderState, bin_lo: int, bin_hi: int):
     """hn_render_bwd_owner: the owner pass of a render_bwd(owner_defer=True)
     over bins [bin_lo, bin_hi) -- their slices of d_table written (or
     stepped, with table_step)."""
-    if getattr(st, "bwd_args", None) is None:
+    if st.bwd_args is None:
         raise RuntimeError("hashnerf_amd.render_bwd_owner: needs a render_bwd(owner_defer=True) first")
     a = st.bwd_args[0]
     L.check(L.lib().hn_render_bwd_owner(st.cfg, a, L.ptr(st.wsb), st.nbytes, bin_lo, bin_hi,
@@ -585,24 +624,8 @@ def render_bwd_rays(st: RenderState, grads: dict) -> torch.Tensor:
     an MLP-weight gradient is formed here.  Bitwise repeatable."""
     B = st.rays.shape[0]
     dev = st.rays.device
-    g_raw_f = grads.get("g_raw_f")
-    if g_raw_f is not None and g_raw_f.numel() != st.raw_f.numel():
-        raise ValueError(f"hashnerf_amd.render_bwd_rays: g_raw_f must be {tuple(st.raw_f.shape)} (the cfg's "
-                         f"n_importance = {_fine_counts(st.cfg)[0]}), got {tuple(g_raw_f.shape)}")
-    a = L.HnRenderBwdArgs()
-    a.n_rays = B
-    a.coarse = L.make_mlp(st.ws[:5])
-    a.fine = L.make_mlp(st.ws[5:])
-    keep = []
-    for k, t in [(n, grads.get(n)) for n in _GRAD_NAMES] + [
-            ("rays", st.rays), ("noise_c", st.noise_c), ("noise_f", st.noise_f), ("table", st.table),
-            ("z_coarse", st.z_c), ("z_fine", st.z_f), ("raw_c", st.raw_c), ("raw_f", st.raw_f)]:
-        L.require_device(t)
-        t = L.contig(t)
-        keep.append(t)
-        setattr(a, k, None if t is None else t.data_ptr())
-    a.fine_src = st.fine_src.data_ptr()
-    a.feat = st.feat.data_ptr()
+    a, keep = _bwd_args("render_bwd_rays", st, grads)
+    L.require_device(*keep)
     d_rays = torch.empty((B, 11), dtype=torch.float32, device=dev)
     nbytes = L.lib().hn_render_bwd_rays_workspace_bytes(st.cfg, B)
     scratch = _ws(nbytes, dev)
@@ -745,11 +768,15 @@ def _ray_ndc(who, ndc):
     return n
 
 
-def _ray_sampler(who, image, c2w, n_rays, K, near, far, crop, seed, morton=True):
-    """What sample_rays and next_batch set up alike: the hn_ray_sampler of one
-    image and window, the contiguous image and [3, 4] pose it is used with,
-    the [n, 11] rays and [n, 3] target to fill and, for the Morton order, the
-    sampler's scratch and its size (None, 0 without)."""
+def _ndc_label(name, nd):
+    """L.check's label of an entry point taking an hn_ray_ndc: the call's name
+    without one (ndc == NULL is that call, bit for bit), else its _ndc name."""
+    return name if nd is None else name + "_ndc"
+
+
+def _ray_sampler(image, c2w, K, near, far, crop, seed):
+    """The hn_ray_sampler of one image and window, and the contiguous image and
+    [3, 4] pose it is used with."""
     L.require_device(image, c2w)
     image, c2w = image.contiguous(), c2w[:3, :4].contiguous()
     s = L.HnRaySampler()
@@ -758,13 +785,13 @@ def _ray_sampler(who, image, c2w, n_rays, K, near, far, crop, seed, morton=True)
     s.fx, s.fy, s.cx, s.cy = float(K[0][0]), float(K[1][1]), float(K[0][2]), float(K[1][2])
     s.near, s.far = float(near), float(far)
     s.seed = int(seed) & ((1 << 64) - 1)
-    nb = L.lib().hn_sample_rays_morton_workspace_bytes(s) if morton else 0
-    if morton and nb == 0:
-        raise ValueError(f"{who}: window {s.crop_h}x{s.crop_w} too large")
-    dev = image.device
-    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
-    target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
-    return s, image, c2w, rays, target, _sampler_ws(dev, nb) if morton else None, nb
+    return s, image, c2w
+
+
+def _batch_out(n_rays, dev):
+    """The [n, 11] rays and [n, 3] target a sampler fills."""
+    return (torch.empty((n_rays, 11), dtype=torch.float32, device=dev),
+            torch.empty((n_rays, 3), dtype=torch.float32, device=dev))
 
 
 class NextBatch:
@@ -774,16 +801,18 @@ class NextBatch:
     __slots__ = ("job", "out", "keep", "ndc")   # ndc: the job's hn_ray_ndc (hn_render_bwd_ndc), or None
 
 
-def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None, ndc=None):
-    """The host half of sample_rays(image, ..., order=1, uniforms=uniforms,
-    ndc=ndc): the sampler's arguments, the output tensors and the default
-    generator's philox offsets (advanced as the torch.rand calls would),
-    without the launches.  render_bwd(next_batch=...) of the binned schedule
-    runs the device half inside its own two small launches, bitwise the values
-    sample_rays would return."""
-    nd = _ray_ndc("next_batch", ndc)
-    s, image, c2w, rays, target, ws, nb = _ray_sampler("next_batch", image, c2w, n_rays, K, near, far, crop, seed)
+def _morton_job(who, image, c2w, n_rays, K, near, far, crop, seed, uniforms, nd):
+    """sample_rays(order=1)'s call as a NextBatch: the hn_ray_sampler, the
+    outputs, the Morton sampler's scratch and the uniform draws (the default
+    generator advanced as the torch.rand calls would advance it), nothing
+    launched.  nd: _ray_ndc's result."""
+    s, image, c2w = _ray_sampler(image, c2w, K, near, far, crop, seed)
+    nb = L.lib().hn_sample_rays_morton_workspace_bytes(s)
+    if nb == 0:
+        raise ValueError(f"{who}: window {s.crop_h}x{s.crop_w} too large")
     dev = image.device
+    rays, target = _batch_out(n_rays, dev)
+    ws = _sampler_ws(dev, nb)
     useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
     j = L.HnNextBatch()
     j.sampler = C.pointer(s)
@@ -796,6 +825,17 @@ def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None, ndc=
     b = NextBatch()
     b.job, b.out, b.keep, b.ndc = j, (rays, target, *outs), (s, image, c2w, ws, arr), nd
     return b
+
+
+def next_batch(image, c2w, n_rays, K, near, far, crop, seed, uniforms=None, ndc=None):
+    """The host half of sample_rays(image, ..., order=1, uniforms=uniforms,
+    ndc=ndc): the sampler's arguments, the output tensors and the default
+    generator's philox offsets (advanced as the torch.rand calls would),
+    without the launches.  render_bwd(next_batch=...) of the binned schedule
+    runs the device half inside its own two small launches, bitwise the values
+    sample_rays would return."""
+    return _morton_job("next_batch", image, c2w, n_rays, K, near, far, crop, seed, uniforms,
+                       _ray_ndc("next_batch", ndc))
 
 
 def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=None, ndc=None):
@@ -817,34 +857,18 @@ def sample_rays(image, c2w, n_rays, K, near, far, crop, seed, order=1, uniforms=
     if order not in (0, 1):
         raise ValueError(f"sample_rays: order {order!r}")
     nd = _ray_ndc("sample_rays", ndc)
-    s, image, c2w, rays, target, ws, nb = _ray_sampler("sample_rays(order=1)", image, c2w, n_rays, K, near, far,
-                                                       crop, seed, morton=order == 1)
-    dev = image.device
     if order == 1:
-        if uniforms:
-            useed, arr, outs = _uniform_draws(uniforms, dev)
-            if nd is None:
-                L.check(L.lib().hn_sample_batch_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
-                                                       L.ptr(target), L.ptr(ws), nb, useed, arr, len(uniforms),
-                                                       L.stream(dev)), "sample_batch_morton")
-            else:
-                L.check(L.lib().hn_sample_batch_morton_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
-                                                           L.ptr(target), L.ptr(ws), nb, useed, arr, len(uniforms),
-                                                           nd, L.stream(dev)), "sample_batch_morton_ndc")
-            return (rays, target, *outs)
-        if nd is None:
-            L.check(L.lib().hn_sample_rays_morton(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target),
-                                                  L.ptr(ws), nb, L.stream(dev)), "sample_rays_morton")
-        else:
-            L.check(L.lib().hn_sample_rays_morton_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays),
-                                                      L.ptr(target), L.ptr(ws), nb, nd, L.stream(dev)),
-                    "sample_rays_morton_ndc")
-    elif nd is None:
-        L.check(L.lib().hn_sample_rays(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target),
-                                       L.stream(dev)), "sample_rays")
-    else:
-        L.check(L.lib().hn_sample_rays_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target), nd,
-                                           L.stream(dev)), "sample_rays_ndc")
+        b = _morton_job("sample_rays(order=1)", image, c2w, n_rays, K, near, far, crop, seed, uniforms, nd)
+        j = b.job
+        L.check(L.lib().hn_sample_batch_morton_ndc(j.sampler, j.image, j.c2w, j.n_rays, j.rays, j.target, j.workspace,
+                                                   j.ws_bytes, j.seed, j.draws, j.n_draws, nd, L.stream(image.device)),
+                _ndc_label("sample_batch_morton" if uniforms else "sample_rays_morton", nd))
+        return b.out
+    s, image, c2w = _ray_sampler(image, c2w, K, near, far, crop, seed)
+    dev = image.device
+    rays, target = _batch_out(n_rays, dev)
+    L.check(L.lib().hn_sample_rays_ndc(s, L.ptr(image), L.ptr(c2w), n_rays, L.ptr(rays), L.ptr(target), nd,
+                                       L.stream(dev)), _ndc_label("sample_rays", nd))
     if uniforms:
         return (rays, target, *torch_uniform(uniforms, dev))
     return rays, target
@@ -891,31 +915,20 @@ def sample_pool(images, poses, image_ids, K, near, far, seed, start, n_rays, ord
     p.near, p.far = float(near), float(far)
     p.seed = int(seed) & ((1 << 64) - 1)
     dev = images.device
-    rays = torch.empty((n_rays, 11), dtype=torch.float32, device=dev)
-    target = torch.empty((n_rays, 3), dtype=torch.float32, device=dev)
+    rays, target = _batch_out(n_rays, dev)
     ids = image_ids.contiguous()
     if order == 1:
         bmin = (C.c_float * 3)(*(float(v) for v in box[0]))
         bmax = (C.c_float * 3)(*(float(v) for v in box[1]))
         keys = torch.empty((n_rays,), dtype=torch.int32, device=dev) if return_keys else None
         useed, arr, outs = _uniform_draws(uniforms, dev) if uniforms else (0, None, [])
-        if nd is None:
-            L.check(L.lib().hn_sample_pool_ordered(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
+        L.check(L.lib().hn_sample_pool_ordered_ndc(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
                                                    int(n_rays), bmin, bmax, L.ptr(rays), L.ptr(target), L.ptr(keys),
-                                                   useed, arr, len(outs), L.stream(dev)), "sample_pool_ordered")
-        else:
-            L.check(L.lib().hn_sample_pool_ordered_ndc(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
-                                                       int(n_rays), bmin, bmax, L.ptr(rays), L.ptr(target),
-                                                       L.ptr(keys), useed, arr, len(outs), nd, L.stream(dev)),
-                    "sample_pool_ordered_ndc")
+                                                   useed, arr, len(outs), nd, L.stream(dev)),
+                _ndc_label("sample_pool_ordered", nd))
         return (rays, target, *outs, keys) if return_keys else (rays, target, *outs)
-    if nd is None:
-        L.check(L.lib().hn_sample_pool(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
-                                       int(n_rays), L.ptr(rays), L.ptr(target), L.stream(dev)), "sample_pool")
-    else:
-        L.check(L.lib().hn_sample_pool_ndc(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start),
-                                           int(n_rays), L.ptr(rays), L.ptr(target), nd, L.stream(dev)),
-                "sample_pool_ndc")
+    L.check(L.lib().hn_sample_pool_ndc(p, L.ptr(images), L.ptr(poses), L.ptr(ids), int(start), int(n_rays),
+                                       L.ptr(rays), L.ptr(target), nd, L.stream(dev)), _ndc_label("sample_pool", nd))
     if uniforms:
         return (rays, target, *torch_uniform(uniforms, dev))
     return rays, target
@@ -967,15 +980,19 @@ def loss_fwd(rgb, rgb0, target, sp, sp0, tv, world, sparse_w, tv_w):
     return out
 
 
+def _loss_grads(rgb, has_rgb0, has_sp0, n_tv):
+    """The tensors hn_loss_bwd / hn_loss_fwd_bwd write: (g_rgb, g_rgb0, g_sp,
+    g_sp0, g_tv), None for a term the loss does not have."""
+    e = lambda n: torch.empty(n, dtype=torch.float32, device=rgb.device)
+    return (torch.empty_like(rgb), torch.empty_like(rgb) if has_rgb0 else None, e(rgb.shape[0]),
+            e(rgb.shape[0]) if has_sp0 else None, e(n_tv) if n_tv else None)
+
+
 def loss_bwd(rgb, rgb0, target, n_tv, world, sparse_w, tv_w, g_loss, has_sp0=True):
     """hn_loss_bwd -> (g_rgb, g_rgb0, g_sp, g_sp0, g_tv) for upstream g_loss (device scalar)."""
     n = rgb.shape[0]
     dev = rgb.device
-    g_rgb = torch.empty_like(rgb)
-    g_rgb0 = torch.empty_like(rgb) if rgb0 is not None else None
-    g_sp = torch.empty(n, dtype=torch.float32, device=dev)
-    g_sp0 = torch.empty(n, dtype=torch.float32, device=dev) if has_sp0 else None
-    g_tv = torch.empty(n_tv, dtype=torch.float32, device=dev) if n_tv else None
+    g_rgb, g_rgb0, g_sp, g_sp0, g_tv = _loss_grads(rgb, rgb0 is not None, has_sp0, n_tv)
     L.check(L.lib().hn_loss_bwd(L.ptr(L.contig(rgb)), L.ptr(L.contig(rgb0)), L.ptr(L.contig(target)), n,
                                 n_tv, float(world), float(sparse_w), float(tv_w), L.ptr(g_loss.contiguous()),
                                 L.ptr(g_rgb), L.ptr(g_rgb0), L.ptr(g_sp), L.ptr(g_sp0), L.ptr(g_tv),
@@ -991,11 +1008,7 @@ def loss_fwd_bwd(rgb, rgb0, target, sp, sp0, tv, world, sparse_w, tv_w, g_loss):
     dev = rgb.device
     n_tv = 0 if tv is None else tv.numel()
     out = torch.empty(4, dtype=torch.float32, device=dev)
-    g_rgb = torch.empty_like(rgb)
-    g_rgb0 = torch.empty_like(rgb) if rgb0 is not None else None
-    g_sp = torch.empty(n, dtype=torch.float32, device=dev)
-    g_sp0 = torch.empty(n, dtype=torch.float32, device=dev) if sp0 is not None else None
-    g_tv = torch.empty(n_tv, dtype=torch.float32, device=dev) if n_tv else None
+    g_rgb, g_rgb0, g_sp, g_sp0, g_tv = _loss_grads(rgb, rgb0 is not None, sp0 is not None, n_tv)
     L.check(L.lib().hn_loss_fwd_bwd(L.ptr(L.contig(rgb)), L.ptr(L.contig(rgb0)), L.ptr(L.contig(target)),
                                     L.ptr(L.contig(sp)), L.ptr(L.contig(sp0)), n, L.ptr(L.contig(tv)), n_tv,
                                     float(world), float(sparse_w), float(tv_w), L.ptr(out),
@@ -1181,7 +1194,6 @@ def _render_views(name, cfg, H, W, K, poses, near, far, table, ws, ndc, t_vals, 
     n = poses.shape[0]
     ni = int(cfg.n_importance) if views else 128
     if t_vals is None:
-        from .render import _linspace_cached
         t_vals = _linspace_cached(64, dev)
     if u is None:
         u = torch.linspace(0., 1., ni, device=dev)
@@ -1218,9 +1230,7 @@ def _render_views(name, cfg, H, W, K, poses, near, far, table, ws, ndc, t_vals, 
     if views:
         va.ndc, va.variant = int(bool(ndc)), int(variant)
         if ndc:
-            # get_ndc_rays' Python scalars (ray_util.py:131-136), float64 here, float32 in the struct
-            focal = float(K[0][0])
-            va.ndc_sx, va.ndc_sy = -1. / (W / (2. * focal)), -1. / (H / (2. * focal))
+            va.ndc_sx, va.ndc_sy = ndc_scalars(H, W, K[0][0])   # float64 here, float32 in the struct
         L.check(lib.hn_render_views(cfg, va, L.ptr(wsb), nbytes, L.stream(dev)), name)
     elif variant:
         L.check(lib.hn_render_image_variant(cfg, a, int(variant), L.ptr(wsb), nbytes, L.stream(dev)),

@@ -13,6 +13,7 @@ kernels too: their backward then forms the ray gradient from the saved state
 """
 from __future__ import annotations
 
+import functools
 import time
 from typing import Optional
 
@@ -22,6 +23,7 @@ import torch
 from . import _lib as L
 from . import functional as HF
 from .embedding import HashEmbedder, SHEncoder
+from .functional import _linspace_cached    # (train and the tests import it from here)
 from .models import NeRFSmall
 from .rays import get_ndc_rays, get_rays
 
@@ -91,20 +93,6 @@ def sample_pdf(bins, weights, N_samples, det=False, pytest=False):
             else np.random.rand(B, N_samples)
         u = torch.tensor(np.ascontiguousarray(u), dtype=torch.float32, device=bins.device)
     return HF.sample_pdf(bins, weights, u)
-
-
-_LINSPACE = {}
-
-
-def _linspace_cached(n, dev):
-    """torch.linspace(0, 1, n) made on the CPU as the reference does (:514),
-    copied to the device once (a per-call pageable copy would stall the
-    host on every training step)."""
-    key = (n, str(dev))
-    t = _LINSPACE.get(key)
-    if t is None:
-        t = _LINSPACE[key] = torch.linspace(0., 1., steps=n).to(dev)
-    return t
 
 
 def _draw(shape, dev, pytest, fn):
@@ -288,19 +276,31 @@ def render_ray_batch(rays_, out_shape, chunk=1024 * 32, **kwargs):
 
 def _image_ineligible(kw) -> Optional[str]:
     """Why render_image cannot render this render() configuration (None: it can)."""
-    if not _fusable(np.empty((0, 11)), kw.get("network_fn"), kw.get("network_query_fn"), kw.get("N_samples"),
-                    kw.get("N_importance", 0), kw.get("network_fine")):
-        return "not the fused HashNeRF configuration (16-level hash grid + SH, two NeRFSmall nets, 64 + 128 samples)"
-    for why, bad in (("N_importance != 128", kw.get("N_importance", 0) != 128),
-                     ("perturb != 0", kw.get("perturb", 0.) != 0.),
-                     ("raw_noise_std != 0", kw.get("raw_noise_std", 0.) != 0.),
-                     ("ndc rays", bool(kw.get("ndc", True))),
-                     ("no view directions (use_viewdirs=False)", not kw.get("use_viewdirs", False)),
-                     ("c2w_staticcam", kw.get("c2w_staticcam") is not None),
-                     ("retraw", bool(kw.get("retraw", False)))):
-        if bad:
-            return why
-    return None
+    why = _views_ineligible(kw)
+    if why is None and kw.get("N_importance", 0) != 128:
+        why = "N_importance != 128"
+    if why is None and kw.get("ndc", True):
+        why = "ndc rays"
+    return why
+
+
+def _whole_image(name, ineligible, call, H, W, K, c2w, kw):
+    """render_image and render_views: the render() configuration kw checked by
+    ``ineligible``, then ``call`` (the functional module's) on its cfg, poses,
+    table and weights."""
+    why = ineligible(kw)
+    if why is not None:
+        raise ValueError(f"hashnerf_amd.{name}: not eligible: {why}")
+    c2w = torch.as_tensor(c2w)
+    L.require_device(c2w)
+    single = c2w.dim() == 2
+    poses = (c2w[None] if single else c2w)[:, :3, :4]
+    emb = kw["network_query_fn"].embed_fn
+    cfg = HF.make_render_cfg(emb.grid(), bool(kw.get("white_bkgd", False)), bool(kw.get("lindisp", False)), False,
+                             n_importance=kw["N_importance"])
+    out = call(cfg, H, W, K, poses, kw.get("near", 0.), kw.get("far", 1.), emb.table,
+               kw["network_fn"].weights() + kw["network_fine"].weights())
+    return tuple(t[0] for t in out) if single else out
 
 
 @torch.no_grad()
@@ -313,19 +313,7 @@ def render_image(H, W, K, c2w, **render_kwargs):
     reason, for a configuration the kernel does not cover: anything but the
     fused HashNeRF configuration, N_importance != 128, perturb, raw noise, ndc,
     no view directions, c2w_staticcam or retraw."""
-    why = _image_ineligible(render_kwargs)
-    if why is not None:
-        raise ValueError(f"hashnerf_amd.render_image: not eligible: {why}")
-    c2w = torch.as_tensor(c2w)
-    L.require_device(c2w)
-    single = c2w.dim() == 2
-    poses = (c2w[None] if single else c2w)[:, :3, :4]
-    kw = render_kwargs
-    emb = kw["network_query_fn"].embed_fn
-    cfg = HF.make_render_cfg(emb.grid(), bool(kw.get("white_bkgd", False)), bool(kw.get("lindisp", False)), False)
-    out = HF.render_image(cfg, H, W, K, poses, kw.get("near", 0.), kw.get("far", 1.), emb.table,
-                          kw["network_fn"].weights() + kw["network_fine"].weights())
-    return tuple(t[0] for t in out) if single else out
+    return _whole_image("render_image", _image_ineligible, HF.render_image, H, W, K, c2w, render_kwargs)
 
 
 def _views_ineligible(kw) -> Optional[str]:
@@ -356,20 +344,8 @@ def render_views(H, W, K, c2w, **render_kwargs):
     table size: no binned backward is needed.  Raises ValueError, naming the
     reason, for perturb, raw noise, no view directions, c2w_staticcam, retraw
     or anything but the fused configuration."""
-    why = _views_ineligible(render_kwargs)
-    if why is not None:
-        raise ValueError(f"hashnerf_amd.render_views: not eligible: {why}")
-    c2w = torch.as_tensor(c2w)
-    L.require_device(c2w)
-    single = c2w.dim() == 2
-    poses = (c2w[None] if single else c2w)[:, :3, :4]
-    kw = render_kwargs
-    emb = kw["network_query_fn"].embed_fn
-    cfg = HF.make_render_cfg(emb.grid(), bool(kw.get("white_bkgd", False)), bool(kw.get("lindisp", False)), False,
-                             n_importance=kw["N_importance"])
-    out = HF.render_views(cfg, H, W, K, poses, kw.get("near", 0.), kw.get("far", 1.), emb.table,
-                          kw["network_fn"].weights() + kw["network_fine"].weights(), ndc=bool(kw.get("ndc", True)))
-    return tuple(t[0] for t in out) if single else out
+    call = functools.partial(HF.render_views, ndc=bool(render_kwargs.get("ndc", True)))
+    return _whole_image("render_views", _views_ineligible, call, H, W, K, c2w, render_kwargs)
 
 
 _IMAGE_GROUP = 8    # views per render_views launch of render_path: bounds the output buffers

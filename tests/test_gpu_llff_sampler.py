@@ -96,6 +96,45 @@ def test_orders_draw_the_same_set(hn):
     assert rows(a) == rows(b) and not torch.equal(a, b)
 
 
+def test_no_draws_through_the_batch_entry_point(hn):
+    """sample_rays(order=1) without uniforms calls hn_sample_batch_morton_ndc
+    with no draws; its rays and target are hn_sample_rays_morton's (world) and
+    hn_sample_rays_morton_ndc's (ndc) for the same sampler, bitwise.  A 16 x 16
+    image, a 12 x 9 window inside it, 37 rays."""
+    from hashnerf_pytorch_amd import functional as HF
+    L = hn._lib
+    g = torch.Generator().manual_seed(3)
+    image = torch.rand((16, 16, 3), generator=g).to(DEV)
+    c2w = torch.tensor([[1., 0., 0., 0.1], [0., 1., 0., -0.2], [0., 0., 1., 0.3]], device=DEV)
+    K = [[20., 0., 8.], [0., 20., 8.], [0., 0., 1.]]
+    crop, n = (2, 5, 12, 9), 37
+    s = L.HnRaySampler()
+    s.H, s.W = 16, 16
+    s.crop_y0, s.crop_x0, s.crop_h, s.crop_w = crop
+    s.fx, s.fy, s.cx, s.cy, s.near, s.far, s.seed = 20., 20., 8., 8., 0., 1., SEED
+    nb = L.lib().hn_sample_rays_morton_workspace_bytes(s)
+    assert nb > 0
+    ws = torch.empty(nb, dtype=torch.uint8, device=DEV)
+    nd = HF._ray_ndc("test", (16, 16, 20.))
+    direct = []
+    for ndc in (None, nd):
+        rays, target = torch.full((n, 11), float("nan"), device=DEV), torch.full((n, 3), float("nan"), device=DEV)
+        if ndc is None:
+            st = L.lib().hn_sample_rays_morton(s, L.ptr(image), L.ptr(c2w), n, L.ptr(rays), L.ptr(target), L.ptr(ws), nb,
+                                               L.stream(DEV))
+        else:
+            st = L.lib().hn_sample_rays_morton_ndc(s, L.ptr(image), L.ptr(c2w), n, L.ptr(rays), L.ptr(target),
+                                                   L.ptr(ws), nb, ndc, L.stream(DEV))
+        assert st == 0
+        assert bool(torch.isfinite(rays).all()) and bool(torch.isfinite(target).all())
+        direct.append((rays, target))
+    assert not torch.equal(direct[0][0], direct[1][0])
+    for ndc, (rays, target) in zip((None, (16, 16, 20.)), direct):
+        got = HF.sample_rays(image, c2w, n, K, 0., 1., crop, SEED, order=1, ndc=ndc)
+        assert len(got) == 2
+        assert torch.equal(got[0], rays) and torch.equal(got[1], target), ndc
+
+
 # ---- 2. pool draws -----------------------------------------------------------------------
 def pool_draw(HF, d, start, n, **kw):
     return HF.sample_pool(d.images, d.poses, d.ids, d.K, 0., 1., 11, start, n, **kw)
