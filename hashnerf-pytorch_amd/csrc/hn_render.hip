@@ -441,6 +441,32 @@ extern "C" int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus) {
   return fwd_pick_form(n_rays, n);
 }
 
+// The resident form's map from (workgroup, run slot) to rays, on the host:
+// fwd_res_deal itself, with the scalar statement of the sort where the kernel
+// uses ballots.  A run that starts past the batch's end has key 0, as in the
+// kernel, whatever run_key says.
+extern "C" int32_t hn_render_fwd_deal(int64_t n_rays, int64_t n_blocks, const uint8_t* run_key,
+                                      int32_t* first_ray) {
+  if (!first_ray) return HN_E_NULL;
+  if (n_rays < 0 || n_blocks < 1 || n_blocks > (INT32_MAX / kFwdResWaves) || n_rays > n_blocks * kFwdResWaves)
+    return HN_E_SHAPE;
+  if (run_key)
+    for (int64_t i = 0; i < n_blocks * kFwdResRuns; ++i)
+      if (run_key[i] > kFwdResRunRays) return HN_E_SHAPE;
+  for (int64_t b = 0; b < n_blocks; ++b) {
+    const int x = (int)(b % kFwdResXcds);
+    auto key_at = [&](int j) {
+      const int64_t run = fwd_res_xcd_run(x, j);
+      return run_key && run * kFwdResRunRays < n_rays ? (int)run_key[run] : 0;
+    };
+    for (int s = 0; s < kFwdResRuns; ++s)
+      first_ray[b * kFwdResRuns + s] = (int32_t)(
+          fwd_res_deal(n_blocks, b, s, [&](int nr, int pos) { return fwd_res_select(nr, pos, key_at); }) *
+          kFwdResRunRays);
+  }
+  return HN_OK;
+}
+
 extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_args* a,
                                  void* workspace, size_t ws_bytes, void* stream) {
   return hn_render_fwd_form(cfg, a, 0, workspace, ws_bytes, stream);

@@ -59,6 +59,103 @@ constexpr int kFwdResWaves = 16;            // the resident form's
 constexpr int kFwdResRuns = 4;              // ... made of this many runs of consecutive rays (the note at `run`)
 constexpr int fwd_block_waves(bool res) { return res ? kFwdResWaves : kFwdBlockWaves; }
 
+// ---- which runs a resident workgroup takes (the note at `run`) -------------
+// Workgroup b runs on XCD b % 8.  Where the deal applies (fwd_res_deal_on) the
+// batch's runs are cut into segments of kFwdResSeg consecutive rays, XCD x
+// owns the segments = x (mod 8), and the XCD's runs -- in batch order -- are
+// stably sorted by descending key (0..kFwdResRunRays: the run's rays whose
+// target is not the background, a stand-in for the colour net's work) and
+// dealt in rounds over the XCD's nb / 8 workgroups, even rounds forward and
+// odd rounds backward: workgroup b / 8 gets one run of each round, a heavy
+// one where its previous was light.  Every other grid keeps the map of
+// fwd_res_band_run.  The functions below are the whole rule, host and device:
+// hn_render_fwd_deal (hn_render.hip) states it through them for the tests and
+// the cost model, the kernel differs only in how it finds the run at a sorted
+// position (fwd_res_select_wave: ballots instead of the scalar scan).
+#ifndef HN_HOST_DEV
+#define HN_HOST_DEV __host__ __device__ inline
+#endif
+constexpr int kFwdResRunRays = kFwdResWaves / kFwdResRuns;   // 4
+constexpr int kFwdResSeg = 64;                                // rays per segment
+constexpr int kFwdResSegRuns = kFwdResSeg / kFwdResRunRays;
+constexpr int kFwdResXcds = 8;
+// the keys of an XCD's runs sit in LDS, one byte each: grids up to 16 x this many rays
+constexpr int kFwdResMaxRuns = 1024;
+static_assert(kFwdResSeg % kFwdResRunRays == 0 && kFwdResMaxRuns % kFwdResSegRuns == 0, "whole runs per segment");
+
+// the runs of an XCD's share (nb / 8 workgroups)
+HN_HOST_DEV int fwd_res_xcd_runs(int64_t nb) { return (int)(nb / kFwdResXcds) * kFwdResRuns; }
+// the deal applies: 8 equal shares, each a whole number of segments that fits the key array
+HN_HOST_DEV bool fwd_res_deal_on(int64_t nb) {
+  return nb > 0 && nb % kFwdResXcds == 0 && nb / kFwdResXcds <= kFwdResMaxRuns / kFwdResRuns &&
+         fwd_res_xcd_runs(nb) % kFwdResSegRuns == 0;
+}
+// run j (batch order) of XCD x's share, as a run of the batch
+HN_HOST_DEV int64_t fwd_res_xcd_run(int x, int j) {
+  return ((int64_t)(j / kFwdResSegRuns) * kFwdResXcds + x) * kFwdResSegRuns + j % kFwdResSegRuns;
+}
+// the sorted position that slot s of the XCD's workgroup w (of nw) takes
+HN_HOST_DEV int fwd_res_deal_pos(int nw, int w, int s) { return s * nw + (s & 1 ? nw - 1 - w : w); }
+// the map without keys, and of every grid the deal does not apply to: the
+// XCD's band of consecutive runs in quarters, one run from each (nb % 8 != 0:
+// the batch in quarters)
+HN_HOST_DEV int64_t fwd_res_band_run(int64_t nb, int64_t block, int s) {
+  return nb % kFwdResXcds == 0
+             ? (block % kFwdResXcds) * (nb / kFwdResXcds * kFwdResRuns) + s * (nb / kFwdResXcds) + block / kFwdResXcds
+             : s * nb + block;
+}
+// the run (of nr, key_at(j) in 0..kFwdResRunRays) at position pos of the stable
+// descending sort: the scalar statement
+template <class KeyAt>
+HN_HOST_DEV int fwd_res_select(int nr, int pos, KeyAt&& key_at) {
+  int cnt[kFwdResRunRays + 1] = {};
+  for (int j = 0; j < nr; ++j) ++cnt[key_at(j)];
+  int b = kFwdResRunRays;
+  for (; b > 0 && pos >= cnt[b]; --b) pos -= cnt[b];
+  for (int j = 0; j < nr; ++j)
+    if (key_at(j) == b && pos-- == 0) return j;
+  return 0;   // (not reached: pos < nr)
+}
+// the run that slot s of workgroup `block` takes; select(nr, pos) = the XCD's
+// run at a sorted position
+template <class Select>
+HN_HOST_DEV int64_t fwd_res_deal(int64_t nb, int64_t block, int s, Select&& select) {
+  if (!fwd_res_deal_on(nb)) return fwd_res_band_run(nb, block, s);
+  const int nw = (int)(nb / kFwdResXcds);
+  return fwd_res_xcd_run((int)(block % kFwdResXcds),
+                         select(fwd_res_xcd_runs(nb), fwd_res_deal_pos(nw, (int)(block / kFwdResXcds), s)));
+}
+// fwd_res_select by one wave, the keys in LDS: the five buckets counted with
+// ballots, then the run whose bucket and rank within it are the position's.
+// Two passes of ceil(nr / 64) steps, or the first alone where all keys are equal.
+HN_DEV int fwd_res_select_wave(const uint8_t* keys, int nr, int pos, int lane) {
+  int cnt[kFwdResRunRays + 1] = {};
+  for (int base = 0; base < nr; base += 64) {
+    const int key = base + lane < nr ? (int)keys[base + lane] : -1;
+#pragma unroll
+    for (int b = 0; b <= kFwdResRunRays; ++b) cnt[b] += __popcll(__ballot(key == b));
+  }
+  int b = kFwdResRunRays;
+#pragma unroll
+  for (int t = kFwdResRunRays; t > 0; --t)
+    if (b == t && pos >= cnt[t]) {
+      pos -= cnt[t];
+      b = t - 1;
+    }
+  // (all runs alike -- no target equals the background, or all do: the sort keeps the batch's order)
+  if (cnt[b] == nr) return __builtin_amdgcn_readfirstlane(pos);
+  int found = 0, seen = 0;
+  for (int base = 0; base < nr; base += 64) {
+    const bool mine = base + lane < nr && (int)keys[base + lane] == b;
+    const uint64_t m = __ballot(mine);
+    const int before = seen + (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+    const uint64_t hit = __ballot(mine && before == pos);
+    if (hit) found = base + __builtin_ctzll(hit);
+    seen += __popcll(m);
+  }
+  return __builtin_amdgcn_readfirstlane(found);
+}
+
 // ---- the ray passes, shared with render_image_kernel -----------------------
 // L: the wave's kFLds floats (the map above), ring: its FragRing slot (kRes:
 // the workgroup's resident sigma regions of the pass's net), gsl: the block's
@@ -262,6 +359,38 @@ void render_fwd_kernel(RenderK k) {
   const int lane = threadIdx.x & 63;
   float* gsl = smem + kBW * kFLds;
   stage_grid_sizes(k.f.g, gsl);
+  const int64_t nb = gridDim.x;
+  // kRes && kLoss: the keys of the XCD's runs (fwd_res_deal), one byte each.
+  // Their own kFwdResMaxRuns bytes, not a region that a wave reuses later: the
+  // waves read them after the kernel's only barrier, each at its own pace.
+  __shared__ uint8_t dkeys[kRes && kLoss ? kFwdResMaxRuns : 4];
+  // A thread per ray of the XCD's share (8 of the 16 waves at 4096 rays; 1.5 KB
+  // of targets per wave, the same for the XCD's workgroups: from L2).  A ray
+  // counts where its target is not the background colour; past the batch's end
+  // none does.  The first 64 x 16 rays' targets are asked for here and looked
+  // at after the sigma copy below, so both are one round trip to memory under
+  // the same barrier.
+  const bool deal = kRes && kLoss && fwd_res_deal_on(nb);
+  const int share = fwd_res_xcd_runs(nb) * kFwdResRunRays;   // deal: a multiple of 64
+  const float bg = k.f.white ? 1.f : 0.f;
+  auto load_targets = [&](int base, float (&t)[3]) {
+    const int lr = base + lane;
+    const int64_t ry = fwd_res_xcd_run((int)(blockIdx.x % kFwdResXcds), lr / kFwdResRunRays) * kFwdResRunRays +
+                       lr % kFwdResRunRays;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) t[c] = ry < k.B ? k.ltarget[3 * ry + c] : bg;
+  };
+  auto store_keys = [&](int base, const float (&t)[3]) {
+    const bool live = fabsf(t[0] - bg) > 1.f / 512 || fabsf(t[1] - bg) > 1.f / 512 || fabsf(t[2] - bg) > 1.f / 512;
+    const uint64_t m = __ballot(live);
+    if (lane < 64 / kFwdResRunRays)
+      dkeys[base / kFwdResRunRays + lane] =
+          (uint8_t)__popcll((m >> (kFwdResRunRays * lane)) & ((1u << kFwdResRunRays) - 1));
+  };
+  float tg[3] = {bg, bg, bg};
+  if constexpr (kRes && kLoss) {
+    if (deal && 64 * wave < share) load_targets(64 * wave, tg);
+  }
   if constexpr (kRes) {
     // every wave of the workgroup, those past the batch's end too: they return
     // only after the barrier
@@ -275,10 +404,16 @@ void render_fwd_kernel(RenderK k) {
       if (j < 2 * kN4) dst[j] = j < kN4 ? srcc[j] : srcf[j - kN4];
     }
   }
+  if constexpr (kRes && kLoss) {
+    if (deal)
+      for (int base = 64 * wave; base < share; base += 64 * kBW) {
+        if (base != 64 * wave) load_targets(base, tg);   // (batches past 8192 rays)
+        store_keys(base, tg);
+      }
+  }
   __syncthreads();
   // XCD-aware: workgroup b runs on XCD b % 8, so consecutive ray groups of a
   // spatially ordered batch go to one XCD and share its L2
-  const int64_t nb = gridDim.x;
   // (round 6, r06k: chunks of 4 or 16 ray groups dealt round-robin over the
   // XCDs, or no XCD mapping at all, were no faster: 234.9 / 228.8 / 240.4 us
   // against 229.4 us -- the forward's per-XCD work is balanced already)
@@ -294,10 +429,23 @@ void render_fwd_kernel(RenderK k) {
     // band of the batch.  Config 2, 4096 rays: render_fwd_kernel 0.2327 ms as
     // 1 run of 16, 0.2216 as 4 runs of 4, 0.2242 as 16 single rays
     // (profiles/r12/); the mean wave is resident for only ~3/4 of the launch.
-    constexpr int kW = kBW / kFwdResRuns;
+    // Which four runs: fwd_res_deal (above).  Where the grid is 8 whole shares
+    // of segments, the runs of the XCD's segments sorted by their keys and
+    // dealt in a snake, so that a workgroup's runs are heavy and light by
+    // cost and not by position, and an XCD's share is spread over the image
+    // instead of one band of it; the keys are the loss mode's, without targets
+    // the runs count alike and the sort keeps the batch's order.  Config 2:
+    // render_fwd_kernel 0.2182 -> 0.2110 ms, the waves resident for 0.78 of
+    // the launch instead of 0.70 (profiles/r18/; a sum-of-costs model said
+    // 0.19 ms: DESIGN 8).  Segments of 32 / 128 / 256 rays: 0.2143 / 0.2117 /
+    // 0.2142 ms; the keys within the XCD's band, no segments: 0.2155; the
+    // segments without keys: 0.2180.
+    constexpr int kW = kFwdResRunRays;
     const int s = wave / kW;
-    const int64_t run = nb % 8 == 0 ? (blockIdx.x % 8) * (nb / 8 * kFwdResRuns) + s * (nb / 8) + blockIdx.x / 8
-                                    : s * nb + blockIdx.x;
+    const int64_t run = fwd_res_deal(nb, blockIdx.x, s, [&](int nr, int pos) {
+      if constexpr (kLoss) return fwd_res_select_wave(dkeys, nr, pos, lane);
+      else return pos;
+    });
     ray = run * kW + wave % kW;   // every ray below 16 nb once; those past the batch's end leave below
   }
   if constexpr (kLoss) {

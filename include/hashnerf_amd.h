@@ -34,7 +34,7 @@ extern "C" {
  * entry points hn_sample_pool_ordered, hn_render_image (with its
  * hn_render_image_workspace_bytes and hn_render_image_variant),
  * hn_render_views (with hn_render_views_workspace_bytes),
- * hn_render_fwd_form and hn_render_fwd_pick, and the input gradients
+ * hn_render_fwd_form, hn_render_fwd_pick and hn_render_fwd_deal, and the input gradients
  * hn_encode_bwd_input, hn_sh_bwd and hn_composite_bwd_inputs. */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
@@ -631,6 +631,22 @@ int32_t hn_render_fwd_form(const hn_render_cfg* cfg, const hn_render_fwd_args* a
 /* The form (1 or 2) hn_render_fwd runs for n_rays on the current device;
  * *cus (optional) = the compute units that rule was stated against. */
 int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus);
+/* Which rays the workgroups of form 2 take (additive under ABI 14; host only,
+ * no device needed: the function the kernel calls, for tests and the cost
+ * model of scripts/fwd_deal_model.py).  Workgroup b of n_blocks (the launch
+ * uses ceil(n_rays / 16)) runs four runs of 4 consecutive rays;
+ * first_ray[4 b + s] = the first ray of its run s, and every multiple of 4
+ * below 16 n_blocks appears once.  run_key [4 n_blocks] (NULL = all equal):
+ * per run of the batch the number of its rays, 0..4, whose target is not the
+ * background colour, which the loss-mode forward counts itself; a run that
+ * starts at or past n_rays counts 0.  Where n_blocks is a multiple of 32 and
+ * at most 2048, XCD b % 8 owns the 64-ray segments = b % 8 (mod 8), sorts
+ * their runs stably by descending key and deals them in rounds over its
+ * n_blocks / 8 workgroups, even rounds forward and odd rounds backward; any
+ * other grid takes one run from each quarter of its XCD's band of the batch
+ * (of the batch, where n_blocks is no multiple of 8).  A key above 4,
+ * n_rays > 16 n_blocks or n_blocks < 1: HN_E_SHAPE. */
+int32_t hn_render_fwd_deal(int64_t n_rays, int64_t n_blocks, const uint8_t* run_key, int32_t* first_ray);
 int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
 
