@@ -215,6 +215,7 @@ SIGNATURES = {
                                        C.c_size_t, _P]),
     "hn_render_fwd_pick": (C.c_int32, [C.c_int64, C.POINTER(C.c_int32)]),
     "hn_render_fwd_deal": (C.c_int32, [C.c_int64, C.c_int64, _P, _P]),
+    "hn_render_fwd_res_map": (C.c_int32, [C.c_int32, _P, C.c_int64, _P, C.c_int64]),
     "hn_render_bwd": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                   C.c_size_t, _P]),
     "hn_render_bwd_ndc": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P, C.c_size_t,

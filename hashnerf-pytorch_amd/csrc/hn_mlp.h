@@ -61,6 +61,65 @@ enum : int {
 };
 static_assert(G_END <= HN_MLP_PACKED_FLOATS, "packed size");
 
+// ---- the resident image of a net (the render forward's 16-wave form) -------
+// What a workgroup of the resident form holds of a packed net in LDS, and
+// where: the map below is the whole rule, host and device (the kernel's copy
+// and FragRes read through it, hn_render_fwd_res_map states it for the tests);
+// it is the same for the coarse and the fine net.  The regions of kResRegs, in
+// that order; of a group's 64 lanes (16 B each, lane = 32 h + output row i)
+// the rows the packing fills: pack_f32 writes R_F1 as i < 16 ? w : 0 and R_F4
+// as i < 3 ? w : 0, so their other lanes are +0 in every part and are not held
+// -- a reader takes literal zero bits for them.  Each run of kept lanes (a
+// 32-lane half's) lies at consecutive addresses, 16 B per lane, so a
+// ds_read_b128 stays conflict-free; every group and region is 16-byte
+// aligned.  R_F1's groups sit in pairs, each lane at its natural place 16 B x
+// lane of a 1-KiB block and the pair's second group in the gaps (+256 B): its
+// reads use the address register of the full regions.  R_F4's 6 kept lanes of
+// a group are packed, half 0's then half 1's.
+//   R_F0 12,288 B | R_F1 rows 0-15 6,144 | R_F2G 6,144 | R_F4 rows 0-2 1,152
+//   = 25,728 B per net.  R_F3 (24 KiB per net) is loaded at use.
+constexpr int kResRegs[] = {R_F0, R_F1, R_F2G, R_F4};
+constexpr int kResRegN = sizeof(kResRegs) / sizeof(kResRegs[0]);
+constexpr bool res_held(int r) { return r == R_F0 || r == R_F1 || r == R_F2G || r == R_F4; }
+// lanes kept of each 32-lane half of a group
+constexpr int res_keep(int r) { return r == R_F1 ? 16 : r == R_F4 ? 3 : 32; }
+constexpr int res_group_floats(int r) { return 8 * res_keep(r); }
+constexpr int res_reg_floats(int r) { return kRegOB[r] * reg_gpo(r) * res_group_floats(r); }
+// float offset of region r in the net's image (r one of kResRegs)
+constexpr int res_reg_off(int r) {
+  int o = 0;
+  for (int i = 0; i < kResRegN && kResRegs[i] != r; ++i) o += res_reg_floats(kResRegs[i]);
+  return o;
+}
+constexpr int kResNetFloats = res_reg_off(R_N);
+// the workgroup's image: the coarse net's, then the fine net's
+constexpr int kResImageFloats = 2 * kResNetFloats;
+constexpr bool res_paired(int r) { return res_keep(r) == 16; }   // groups in pairs, lanes at their natural places
+// float offset of group t = ob * reg_gpo(r) + g of a held region r
+constexpr int res_group_off(int r, int t) {
+  return res_reg_off(r) + (res_paired(r) ? (t >> 1) * 256 + (t & 1) * 64 : t * res_group_floats(r));
+}
+// a lane's 4 floats relative to its group's offset, or -1: a zero lane
+constexpr int res_lane_off(int r, int lane) {
+  return (lane & 31) >= res_keep(r) ? -1 : res_keep(r) == 3 ? 4 * ((lane >> 5) * 3 + (lane & 31)) : 4 * lane;
+}
+// image offset of (region, group, lane)'s 16 bytes, or -1 (not held, or a zero lane)
+constexpr int res_at(int r, int t, int lane) {
+  return res_held(r) && res_lane_off(r, lane) >= 0 ? res_group_off(r, t) + res_lane_off(r, lane) : -1;
+}
+// the packed-net float that float i of the net's image is a copy of
+constexpr int res_src(int i) {
+  int r = kResRegs[0];
+  for (int k = 1; k < kResRegN; ++k)
+    if (i >= res_reg_off(kResRegs[k])) r = kResRegs[k];
+  const int rel = i - res_reg_off(r), gf = res_paired(r) ? 256 : res_group_floats(r), keep = res_keep(r);
+  const int w = rel % gf, l = w >> 2;   // l: the 16-byte place in the group (paired: in the pair's block)
+  const int t = res_paired(r) ? 2 * (rel / gf) + ((l >> 4) & 1) : rel / gf;
+  const int lane = res_paired(r) ? (l & 15) + (l & 32) : 32 * (l / keep) + l % keep;
+  return reg_off(r) + t * 256 + 4 * lane + (w & 3);
+}
+static_assert(kResNetFloats * 4 == 25728 && res_reg_off(R_F4) * 4 == 24576, "the resident image's budget");
+
 // Weight-gradient accumulator layout (torch [out][in] row-major, concatenated).
 enum : int { W_S0 = 0, W_S1 = 2048, W_C0 = 3072, W_C1 = 5056, W_C2 = 9152, W_END = 9344 };
 static_assert(W_END == HN_MLP_PARAMS, "param count");
@@ -79,7 +138,7 @@ static_assert(W_END == HN_MLP_PARAMS, "param count");
 // memory: frag_load).
 struct FragGlobal {
   static constexpr bool kRing = false;
-  static constexpr int kLdsEnd = 0;   // no region is read from LDS
+  static constexpr bool kRes = false;   // no region is read from LDS
   const float* P;
   HN_DEV f32x4 operator()(int off, int lane) const { return frag_load(P, off, lane); }
 };
@@ -109,24 +168,36 @@ constexpr int fwd_next_off(int r, int ob, int c) {
 // net's first chunk in the slot before its tiles.
 struct FragRing {
   static constexpr bool kRing = true;
-  static constexpr int kLdsEnd = 0;
+  static constexpr bool kRes = false;
   const float* P;
   float* slot;   // LDS, this wave's 768 floats
   HN_DEV f32x4 operator()(int off, int lane) const { return frag_load(P, off, lane); }
 };
-// The sigma net resident (the render forward's 16-wave form): the regions below
-// G_F2G -- R_F0 and R_F1, the packed net's first kFragResFloats floats, every
-// tile's 8 chunks -- are read from a copy of them the workgroup holds in LDS,
-// as packed, at compile-time offsets: no vmcnt wait, no refill.  The colour
-// regions (only tiles with density run them) are loaded at use, as FragGlobal.
-constexpr int kFragResFloats = G_F2G;
+// The resident form of the render forward (16-wave workgroups): the regions
+// the net's resident image holds (the map at kResRegs: both sigma regions,
+// R_F2G and R_F4) are read from the copy the workgroup made in LDS, at
+// compile-time offsets: no vmcnt wait, no refill.  A zero lane of R_F1 / R_F4
+// reads nothing and holds +0, the bits the packed buffer has there, so every
+// operand register equals the ring form's.  R_F3 is loaded at use, as
+// FragGlobal.
 struct FragRes {
   static constexpr bool kRing = false;
-  static constexpr int kLdsEnd = kFragResFloats;   // region offsets below this are read from res
+  static constexpr bool kRes = true;
   const float* P;
-  const float* res;   // LDS, the workgroup's P[0 .. kFragResFloats)
+  const float* res;   // LDS, the workgroup's image of this net
   HN_DEV f32x4 operator()(int off, int lane) const { return frag_load(P, off, lane); }
-  HN_DEV f32x4 lds(int off, int lane) const { return *reinterpret_cast<const f32x4*>(res + off + 4 * lane); }
+  // group t = ob * reg_gpo(R) + g of region R
+  template <int R>
+  HN_DEV f32x4 lds(int t, int lane) const {
+    const float* g = res + res_group_off(R, t);
+    if constexpr (res_keep(R) == 32) {
+      return *reinterpret_cast<const f32x4*>(g + 4 * lane);
+    } else {
+      f32x4 v = {0.f, 0.f, 0.f, 0.f};
+      if ((lane & 31) < res_keep(R)) v = *reinterpret_cast<const f32x4*>(g + res_lane_off(R, lane));
+      return v;
+    }
+  }
 };
 HN_DEV void ring_fill(const float* P, float* slot, int off, int lane) {
   int so = off * 4;
@@ -151,10 +222,12 @@ template <int R, typename BF, typename Src>
 HN_DEV f32x16 gemm_src(const Src& src, int ob, f32x16 acc, int lane, BF bval) {
   constexpr int KS = kRegKS[R], NS = reg_ns(R), GPO = reg_gpo(R), OFF = reg_off(R);
   // fragment group g of this block (frag_load: scalar offsets, hn_common.h)
-  auto ld = [&](int g) {
-    if constexpr (OFF < Src::kLdsEnd) return src.lds(OFF + (ob * GPO + g) * 256, lane);   // a resident region
-    else return src(OFF + (ob * GPO + g) * 256, lane);
-  };
+  auto ld = [&](int g) { return src(OFF + (ob * GPO + g) * 256, lane); };
+  // (a resident region with packed lanes: the lane's place among the kept ones
+  // is formed in this GEMM, not hoisted out of the tile loop and held in
+  // VGPRs across it -- that put scratch reloads into the tile loops)
+  int rl = lane;
+  if constexpr (Src::kRes && res_keep(R) == 3) asm volatile("" : "+v"(rl));
   if constexpr (NS > 0) {        // split-f32, fragments loaded at use
 #pragma unroll
     for (int c = 0; c < KS / 8; ++c) {
@@ -166,6 +239,9 @@ HN_DEV f32x16 gemm_src(const Src& src, int ob, f32x16 acc, int lane, BF bval) {
         for (int q = 0; q < NS; ++q) a.p[q] = as_bf16x8(*reinterpret_cast<const f32x4*>(src.slot + 256 * q + 4 * lane));
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         ring_fill(src.P, src.slot, fwd_next_off(R, ob, c), lane);
+      } else if constexpr (Src::kRes && res_held(R)) {   // from the net's resident image
+#pragma unroll
+        for (int q = 0; q < NS; ++q) a.p[q] = as_bf16x8(src.template lds<R>(ob * GPO + NS * c + q, rl));
       } else {
 #pragma unroll
         for (int q = 0; q < NS; ++q) a.p[q] = as_bf16x8(ld(NS * c + q));

@@ -467,6 +467,22 @@ extern "C" int32_t hn_render_fwd_deal(int64_t n_rays, int64_t n_blocks, const ui
   return HN_OK;
 }
 
+// The resident form's image of a net, on the host: res_src and res_at
+// themselves (hn_mlp.h), the functions the kernel's copy and FragRes read
+// through.
+extern "C" int32_t hn_render_fwd_res_map(int32_t fine, int32_t* src, int64_t n_src, int32_t* at, int64_t n_at) {
+  if (fine < 0 || fine > 1) return -HN_E_SHAPE;
+  const int n = kResNetFloats;   // (the two nets' images are laid out alike)
+  if ((src && n_src < n) || (at && n_at < G_B4 / 4)) return -HN_E_SHAPE;
+  if (src)
+    for (int i = 0; i < n; ++i) src[i] = res_src(i);
+  if (at)
+    for (int r = R_F0; r < R_B4; ++r)
+      for (int t = 0; t < kRegOB[r] * reg_gpo(r); ++t)
+        for (int lane = 0; lane < 64; ++lane) at[reg_off(r) / 4 + t * 64 + lane] = res_at(r, t, lane);
+  return n;
+}
+
 extern "C" int32_t hn_render_fwd(const hn_render_cfg* cfg, const hn_render_fwd_args* a,
                                  void* workspace, size_t ws_bytes, void* stream) {
   return hn_render_fwd_form(cfg, a, 0, workspace, ws_bytes, stream);

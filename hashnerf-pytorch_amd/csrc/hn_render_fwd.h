@@ -43,12 +43,15 @@ constexpr int kFwdWavesPerSimd = 4;
 //     wave's private 3-KiB LDS ring (FragRing), one buffer_load ... lds round
 //     trip per chunk;
 //   resident (kRes = true): 16-wave workgroups, one per CU.  The workgroup
-//     copies the sigma regions of both packed nets (Pc, Pf [0, kFragResFloats),
-//     2 x 24 KiB) into LDS once, ahead of the kernel's only barrier, and
-//     sigma_net.0 / .1 -- 8 of a tile's 22 chunks, and all of a tile without
-//     density -- read them there (FragRes): no vmcnt wait, no refill, no
-//     reload at the pass switch.  The colour net's chunks are loaded at use.
-//     LDS: 16 x kFLds + kGsLds + 2 x kFragResFloats floats = 143,744 B.
+//     gathers the resident image of both packed nets (the map at kResRegs,
+//     hn_mlp.h: sigma_net.0, sigma_net.1, color_net.0's geo half and
+//     color_net.2, the zero rows of sigma_net.1 and color_net.2 packed out;
+//     2 x 25,728 B) into LDS once, ahead of the kernel's only barrier, and
+//     those regions -- 14 of a tile's 22 chunks, and all of a tile without
+//     density -- are read there (FragRes): no vmcnt wait, no refill, no
+//     reload at the pass switch.  color_net.1's 8 chunks are loaded at use.
+//     LDS: 16 x kFLds + kGsLds + kResImageFloats floats = 146,048 B (+ the
+//     loss mode's 1,024 key bytes).
 // (Round 4's whole-net-in-LDS form, one net at a time with a reload and a
 // barrier at the pass switch, every tile 22 chunks, lost 0.294 to 0.281 ms:
 // the 16 waves marched in step; profiles/r04/r04e, r04f.)
@@ -158,7 +161,7 @@ HN_DEV int fwd_res_select_wave(const uint8_t* keys, int nr, int pos, int lane) {
 
 // ---- the ray passes, shared with render_image_kernel -----------------------
 // L: the wave's kFLds floats (the map above), ring: its FragRing slot (kRes:
-// the workgroup's resident sigma regions of the pass's net), gsl: the block's
+// the workgroup's resident image of the pass's net), gsl: the block's
 // staged grid sizes.  A policy Pol, every hook inline (pass: 0 coarse,
 // 1 fine, a constant at each call):
 //   kMasks           the tiles' ReLU masks are formed
@@ -235,6 +238,19 @@ HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L,
       asm volatile("" : "+s"(zero));
       gsl += zero;
     }
+    // (the resident image's address likewise: the per-lane LDS addresses of
+    // its regions are formed in the tile, against one base, instead of one
+    // VGPR per 64-KiB window and lane pattern held across both tile loops;
+    // and the lane of the feature, mask and raw stores and of the encode's
+    // level offsets, whose per-lane addresses were otherwise held across the
+    // loop and reloaded from scratch in every tile)
+    int lane_s = lane;
+    if constexpr (kRes) {
+      int zero = 0;
+      asm volatile("" : "+s"(zero));
+      ring += zero;
+      lane_s += zero;
+    }
     const int q = 32 * tau + p;
     float pt[3];
     ray_point(r, L[(kPass ? kFZs : kFZc) + q], pt);
@@ -251,7 +267,7 @@ HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L,
     const int src = twins ? pol.origin(q) : 255;
     if (src >= kSc) {
       HN_FWD_PRIO_HI();
-      encode_tile(f.g, gsl, f.table, pt, h, feat);
+      encode_tile(f.g, gsl, f.table, pt, lane_s >> 5, feat);
       HN_FWD_PRIO_LO();
     } else {
       load_twin_feat(twins, src, h, feat);
@@ -263,18 +279,18 @@ HN_DEV void pass_tiles(const FieldK& f, const float* gsl, float* ring, float* L,
     // features or masks -- they are not stored.  (The coarse tiles' are: the twins.)
     const bool dead_skip = pol.skip_dead(kPass);
     bool stored = kPass == 0 || !dead_skip;
-    if (stored) pol.save_feat(kPass, tau, lane, feat);
+    if (stored) pol.save_feat(kPass, tau, lane_s, feat);
     using Src = std::conditional_t<kRes, FragRes, FragRing>;
     mlp_fwd_tile_src<Pol::kMasks>(Src{P, ring}, feat, [&](int ob) { return c0sh_lds_load(L + kFC0, ob, lane); },
                                   a, c2, lane, dead_skip, [&]() {
-                                    if (!stored) pol.save_feat(kPass, tau, lane, feat);
+                                    if (!stored) pol.save_feat(kPass, tau, lane_s, feat);
                                     stored = true;
                                   });
     const float4 o4 = make_float4(c2[0], c2[1], c2[2], a.s1[0]);
-    if (stored) pol.save_masks(kPass, tau, lane, a.m);
+    if (stored) pol.save_masks(kPass, tau, lane_s, a.m);
     if (h == 0) {
       *reinterpret_cast<float4*>(L + kFRaw + 4 * q) = o4;
-      pol.save_raw(kPass, q, o4);
+      pol.save_raw(kPass, 32 * tau + (lane_s & 31), o4);
     }
   }
 }
@@ -348,10 +364,10 @@ void render_fwd_kernel(RenderK k) {
   __shared__ __attribute__((aligned(16))) float smem[kBW * kFLds + kGsLds];
   // each wave's split-GEMM fragments one chunk ahead (FragRing, hn_mlp.h):
   // render_fwd_kernel 0.271 -> 0.266 ms, r05 ring (bitwise-identical outputs);
-  // kRes: the array holds the workgroup's resident sigma regions instead, the
-  // coarse net's, then the fine net's (the same 768 floats per wave)
-  static_assert(2 * kFragResFloats % (4 * kFwdResWaves) == 0, "a whole dwordx4 share per wave");
-  __shared__ __attribute__((aligned(16))) float fring[kBW][kRes ? 2 * kFragResFloats / kFwdResWaves : 768];
+  // kRes: the array holds the workgroup's resident image instead, the coarse
+  // net's, then the fine net's (804 floats per wave)
+  static_assert(kResImageFloats % (4 * kFwdResWaves) == 0, "a whole dwordx4 share per wave");
+  __shared__ __attribute__((aligned(16))) float fring[kBW][kRes ? kResImageFloats / kFwdResWaves : 768];
   // the wave index (and with it the ray, its 11 floats and every per-ray
   // address) on the scalar unit: VGPR spills 45 -> 22, render_fwd_kernel
   // 0.296 -> 0.281 ms (r04e)
@@ -394,14 +410,17 @@ void render_fwd_kernel(RenderK k) {
   if constexpr (kRes) {
     // every wave of the workgroup, those past the batch's end too: they return
     // only after the barrier
-    constexpr int kN4 = kFragResFloats / 4;   // dwordx4 per net
+    // the workgroup's image (the map at kResRegs, hn_mlp.h): dwordx4 j of it
+    // from the packed net's dwordx4 res_src / 4 -- the kept lanes of a group
+    // are consecutive in both, a zero lane is not copied
+    constexpr int kN4 = kResImageFloats / 4, kC4 = kResNetFloats / 4;   // dwordx4: the image's, one net's
     const f32x4* srcc = reinterpret_cast<const f32x4*>(k.f.Pc);
     const f32x4* srcf = reinterpret_cast<const f32x4*>(k.f.Pf);
     f32x4* dst = reinterpret_cast<f32x4*>(&fring[0][0]);
 #pragma unroll
-    for (int i = 0; i < (2 * kN4 + 64 * kBW - 1) / (64 * kBW); ++i) {
+    for (int i = 0; i < (kN4 + 64 * kBW - 1) / (64 * kBW); ++i) {
       const int j = i * 64 * kBW + (int)threadIdx.x;
-      if (j < 2 * kN4) dst[j] = j < kN4 ? srcc[j] : srcf[j - kN4];
+      if (j < kN4) dst[j] = (j < kC4 ? srcc : srcf)[res_src(4 * (j < kC4 ? j : j - kC4)) >> 2];
     }
   }
   if constexpr (kRes && kLoss) {
@@ -486,7 +505,7 @@ void render_fwd_kernel(RenderK k) {
   TrainTiles<kLoss, kSfT> pol{k, ray, srcl};
   // the passes' fragment source: the wave's ring slot, or the net's resident regions
   float* srcc = kRes ? &fring[0][0] : fring[wave];
-  float* srcf = kRes ? &fring[0][0] + kFragResFloats : fring[wave];
+  float* srcf = kRes ? &fring[0][0] + kResNetFloats : fring[wave];
   pass_start<kRes>(k.f.Pc, sh8, L, srcc, lane, false);
   pass_tiles<0, TrainTiles<kLoss, kSfT>, kSf, kRes>(k.f, gsl, srcc, L, r, lane, pol);
   lds_fence_wave();

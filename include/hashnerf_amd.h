@@ -34,7 +34,8 @@ extern "C" {
  * entry points hn_sample_pool_ordered, hn_render_image (with its
  * hn_render_image_workspace_bytes and hn_render_image_variant),
  * hn_render_views (with hn_render_views_workspace_bytes),
- * hn_render_fwd_form, hn_render_fwd_pick and hn_render_fwd_deal, and the input gradients
+ * hn_render_fwd_form, hn_render_fwd_pick, hn_render_fwd_deal and
+ * hn_render_fwd_res_map, and the input gradients
  * hn_encode_bwd_input, hn_sh_bwd and hn_composite_bwd_inputs. */
 #define HN_ABI_VERSION 14
 #define HN_MAX_LEVELS 32
@@ -647,6 +648,21 @@ int32_t hn_render_fwd_pick(int64_t n_rays, int32_t* cus);
  * (of the batch, where n_blocks is no multiple of 8).  A key above 4,
  * n_rays > 16 n_blocks or n_blocks < 1: HN_E_SHAPE. */
 int32_t hn_render_fwd_deal(int64_t n_rays, int64_t n_blocks, const uint8_t* run_key, int32_t* first_ray);
+/* What a workgroup of form 2 holds of a packed net in LDS (additive under ABI
+ * 14; host only, no device needed: the functions the kernel copies and reads
+ * through, for the tests).  fine: 0 the coarse net, 1 the fine net (the two
+ * are laid out alike).  Returns the floats of that net's image (the
+ * workgroup's image is the coarse net's, then the fine net's): sigma_net.0,
+ * rows 0-15 of sigma_net.1, color_net.0's geo half and rows 0-2 of
+ * color_net.2.  src [n_src] (optional): for every float of the image
+ * the index of the packed-net float it is a copy of.  at [n_at] (optional,
+ * n_at >= 4608: one entry per 16-byte lane of the forward regions, the packed
+ * float index / 4): the image's float offset of that lane's 4 floats, or -1
+ * where the image does not hold them -- a region that is loaded at use
+ * (color_net.1, color_net.0's SH half), or a lane the packing leaves zero (output rows 16-31 of sigma_net.1, 3-31 of
+ * color_net.2), for which the kernel takes zero bits.  fine outside 0..1 or an
+ * array too short: -HN_E_SHAPE. */
+int32_t hn_render_fwd_res_map(int32_t fine, int32_t* src, int64_t n_src, int32_t* at, int64_t n_at);
 int32_t hn_render_bwd(const hn_render_cfg* cfg, const hn_render_bwd_args* a,
                       void* workspace, size_t ws_bytes, void* stream);
 
