@@ -20,7 +20,7 @@ from __future__ import annotations
 import math
 import types
 import warnings
-from typing import Optional
+from typing import NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -568,19 +568,30 @@ def _step_seed(seed, rank, step):
     return x ^ (x >> 31)
 
 
+class StepPlan(NamedTuple):
+    """The launches of one explicit-mode step, decided in Trainer._plan alone at the top of the step."""
+    binned: bool            # backward by records + owner pass (else the float-atomic scatter)
+    skip_dead_color: bool   # forward: no colour net, features or masks for tiles without density
+    fuse_loss: bool         # no hn_loss_fwd_bwd launch: the render backward forms loss and gradients
+    fold_prepass: bool      # no composite pre-pass launch: the forward's own waves run it
+    table_in_owner: bool    # the table's RAdam step inside the owner pass; its gradient is never stored
+    mlp_in_slab: bool       # no hn_radam_step launch: the MLP steps + repack inside the slab reduction
+    owner_defer: bool       # no owner pass in the backward: the DP exchange runs it segment by segment
+    prefetch: bool          # the next batch's sampler launches on a side stream, beside the backward
+    next_in_bwd: bool       # no sampler launches: the backward's lists / placement launches draw batch i + 1
+
+
 class Trainer:
     """One training iteration of run_nerf.py:541-651.
 
-    mode="explicit" (default): the step as an explicit launch sequence -- device
-    ray sampler, fused render forward, TV forward, fused loss forward and
-    backward, render backward and TV backward accumulating into ONE persistent
-    table-gradient buffer, all-reduce, RAdam -- with no autograd graph (the
-    gradients are those autograd computes for the same loss: the loss
-    backward reproduces autograd's op order, the render/TV backwards are the
-    Functions' own backwards).  mode="autograd": the same kernels through the
-    autograd module API (render_rays, TrainLossFn, TVFn).  mode="eager": the
-    module API with eager torch sampling and loss ops (randperm, img2mse,
-    sums), the op-for-op rendition of run_nerf.py."""
+    mode="explicit" (default): the step as an explicit launch sequence -- device ray sampler, fused
+    render forward, TV forward, fused loss forward and backward, render backward and TV backward
+    accumulating into ONE persistent table-gradient buffer, all-reduce, RAdam -- with no autograd graph
+    (the gradients are those autograd computes for the same loss: the loss backward reproduces
+    autograd's op order, the render/TV backwards are the Functions' own backwards); StepPlan names
+    the launches its flags fuse away.  mode="autograd": the same kernels through the autograd module
+    API (render_rays, TrainLossFn, TVFn).  mode="eager": the module API with eager torch sampling and
+    loss ops (randperm, img2mse, sums), the op-for-op rendition of run_nerf.py."""
 
     def __init__(self, args, data: SyntheticBlender, device, rank=0, world=1, seed=0, mode="explicit",
                  ray_order=1, pool_order=0):
@@ -629,7 +640,8 @@ class Trainer:
                                 torch.arange(W // 2 - dW, W // 2 + dW, device=self.device), indexing="ij")
         self.coords_crop = torch.stack([cj, ci], -1).reshape(-1, 2)
         self.crop = (H // 2 - dH, W // 2 - dW, 2 * dH, 2 * dW)
-        self._grads = None
+        self._cfg = None         # the render cfg: None until _fused_setup has run
+        self._live = self._livem = False   # live_rows / live_pair_mask on the device: False = not computed yet
         # use_batching (no_batching False, e.g. configs/scannet_scene0000.txt:6):
         # the global shuffled ray pool of run_nerf.py:505-521 over the training
         # images, consumed N_rand positions per step and reshuffled per epoch
@@ -641,79 +653,80 @@ class Trainer:
         if self.use_batching:
             self._pool_ids = torch.as_tensor(data.i_train).to(device=self.device, dtype=torch.int32)
             self._pool_n = int(self._pool_ids.numel()) * H * W
-        # the render backward's sticky fault word (hn_device_faults) is read
-        # every this many steps: one blocking copy, so a failed internal wait
-        # can never leave silently wrong gradients behind for long
+        # the render backward's sticky fault word (hn_device_faults) is read every this many steps:
+        # one blocking copy, so a failed internal wait never leaves wrong gradients behind for long
         self.fault_check_every = 100
-        # explicit mode, one GPU: fuse the table's RAdam step into the binned
-        # backward's owner pass when the step has no TV term
+        # The ten flags of the explicit-mode step.  They say what is asked for; where each takes
+        # effect is decided by _plan() alone, afresh every step, so a caller may flip them between steps.
+        # the table's RAdam step inside the binned backward's owner pass
         self.fuse_table_step = True
-        # ... and skip the coarse levels' unreachable row pairs there
-        # (live_pair_mask: bitwise the same step, fewer optimizer-state bytes)
+        # ... skipping the coarse levels' unreachable row pairs there (live_pair_mask: bitwise the same step)
         self.skip_dead_rows = True
-        # explicit mode, world > 1: reduce-scatter / sharded RAdam / all-gather
-        # of the table (ShardedTableStep) instead of all-reduce + full RAdam
+        # world > 1: reduce-scatter / sharded RAdam / all-gather of the table
+        # (ShardedTableStep, built at setup) instead of all-reduce + full RAdam
         self.dp_sharded = True
-        # ... in this many bin-aligned segments, each exchanged as soon as the
-        # backward's owner pass has formed it (1: one exchange after the whole
-        # backward).  1 by default: the segmented form's RCCL overlap (segment
-        # k's reduce-scatter on RCCL's stream while the owner pass forms
-        # segment k+1) has run only on gloo so far; the GPU DP
-        # tests and bench.py --dp-chunks select it
+        # ... in this many bin-aligned segments, each exchanged as soon as the owner pass has formed
+        # it.  1 by default: the segmented form's RCCL overlap has run only on gloo so far (ADVICE
+        # r04); the GPU DP tests and bench.py --dp-chunks select it
         self.dp_chunks = 1
-        self._xchg = None
-        self._owner_st = None
-        # self-driving loops (bench.py): the next step's batch -- device ray
-        # sampler and the jitter / importance uniforms -- is drawn on a side
-        # stream as soon as this step's forward is enqueued, so it runs beside
-        # the backward instead of ahead of the next forward.  The draws and
-        # their order are those of draw_batch at the start of the next step
-        # (bitwise the same trajectory).  Opt-in: a caller that draws its own
-        # batches (draw_batch + step(i, batch)) must leave it off, or the
-        # prefetch consumes the next step's random numbers first.  Measured
-        # slower at config 2 (r05k: 0.996 vs 0.982 ms per step: the
-        # cross-stream waits cost more than the launches they move), so off
-        # unless asked for (bench.py --prefetch).
+        self._xchg = self._owner_st = None
+        # self-driving loops (bench.py): the next step's batch is drawn on a side stream as soon as
+        # this step's forward is enqueued, in draw_batch's order (bitwise the same trajectory).
+        # Opt-in: a caller that draws its own batches must leave it off, or the prefetch consumes
+        # the next step's random numbers first.  Measured slower at config 2 (r05k: 0.996 vs
+        # 0.982 ms per step: the cross-stream waits cost more than the launches they move)
         self.prefetch = False
-        # self-driving loops again, without a second stream: the next step's
-        # batch is drawn inside this step's render backward, whose two small
-        # launches (work lists, overflow placement) leave nearly every CU
-        # idle and take the sampler's two passes as extra workgroups
-        # (hn_render_bwd_args.next_batch) -- no sampler launch ahead of the
-        # next forward.  In effect only where _fuses_next_batch() holds (one
-        # GPU, binned schedule with the fused table step, the per-image Morton
-        # sampler, prefetch off: the two cannot both draw the next batch, and
-        # prefetch, the one asked for, wins) and only in a step() called
-        # without an index or a batch.  Step i then draws batch i + 1 in
-        # draw_batch's order (image, philox offsets, TV cubes) before its
-        # backward, and draw_batch(i + 1) hands that batch out -- to the next
-        # step() or to a caller -- so every trajectory is bitwise the same.
+        # ... or, without a second stream, as extra workgroups of this step's render backward
+        # (hn_render_bwd_args.next_batch): step i draws batch i + 1 in draw_batch's order and draw_batch(i + 1)
+        # hands it out, so every trajectory is bitwise the same.  Where both are asked for, prefetch draws
         self.fuse_next_batch = True
         self._nb = None          # (step, batch) drawn by the previous step's backward
         self._binned = False     # (set by _fused_setup)
-        # one GPU, fused table step: the MLP tensors' RAdam steps run in the
-        # backward's slab reduction too (no hn_radam_step launch)
+        # the MLP tensors' RAdam steps in the backward's slab reduction (no hn_radam_step launch),
+        # which then repacks them into the render workspace, kept across steps, for the next forward
         self.fuse_mlp_step = True
-        # ... and then repacks them for the next forward, which reuses the
-        # render workspace (kept across steps) instead of packing again
         self._rws = None         # the render workspace
         self._rws0 = None        # an empty rank's TV-only workspace (before any render)
         self._pk = None          # (workspace, weight versions) its packed copies belong to
-        self._pf = None          # (step, batch, ready event) drawn ahead
-        # explicit mode: the loss value and its gradients formed by the render
-        # backward's composite pre-pass (ABI 13) instead of an hn_loss_fwd_bwd
-        # launch
+        self._pf = self._side = None   # (step, batch, ready event) drawn ahead (prefetch); its side stream
+        # the loss and its gradients formed by the render backward's composite pre-pass (ABI 13)
         self.fuse_loss = True
-        # ... and, one GPU with the binned backward, that composite backward run by
-        # the forward's own waves on the raw / z they still hold (no pre-pass
-        # launch; False keeps the pre-pass, for the A/B: bitwise the same step)
+        # ... and that pre-pass run by the forward's own waves on the raw / z they still hold
+        # (False keeps the pre-pass launch, for the A/B: bitwise the same step)
         self.fuse_prepass = True
-        self._side = None
-        # the backward skips the samples whose d raw is exactly zero (relu(sigma)
-        # = 0: no gradient at all; hn_render_cfg.dense_bwd, ABI 14): True
-        # computes them too (A/B: bench.py --dense-bwd; same results up to the
-        # sign of zero)
+        # True: the backward also computes the samples whose d raw is exactly zero (relu(sigma) = 0: no gradient;
+        # A/B: bench.py --dense-bwd, same results up to the sign of zero).  After setup: hn_render_cfg.dense_bwd
         self.dense_bwd = False
+
+    @property
+    def dense_bwd(self) -> bool:
+        return self._dense_bwd if self._cfg is None else bool(self._cfg.dense_bwd)
+
+    @dense_bwd.setter
+    def dense_bwd(self, on):
+        self._dense_bwd = bool(on)
+        if self._cfg is not None:
+            self._cfg.dense_bwd = int(self._dense_bwd)
+
+    def _drop_setup(self):
+        """Forget the explicit step's setup: the next step builds it, and the DP exchange, again."""
+        self._cfg = self._xchg = None
+
+    def _plan(self, batch_given=False, self_driven=False) -> StepPlan:
+        """This step's launches, from the flags as they stand now."""
+        binned, cuda = self._binned, self.device.type == "cuda"
+        table_in_owner = self.fuse_table_step and self.world == 1 and binned
+        # next_in_bwd: the backward must run the lists / placement launches and the owner pass
+        # itself, and the batch must be the per-image Morton sampler's with its uniform draws
+        next_in_bwd = (table_in_owner and self_driven and self.fuse_next_batch and not self.prefetch
+                       and self.mode == "explicit" and cuda and not self.use_batching and self.ray_order == 1
+                       and self.kw_train.get("perturb", 0.) > 0.)
+        return StepPlan(
+            binned=binned, skip_dead_color=not self.dense_bwd and binned, fuse_loss=bool(self.fuse_loss),
+            fold_prepass=bool(self.fuse_prepass and self.fuse_loss and binned and self.world == 1),
+            table_in_owner=bool(table_in_owner), mlp_in_slab=bool(table_in_owner and self.fuse_mlp_step),
+            owner_defer=not table_in_owner and self._xchg is not None and self._xchg.seg_bins is not None,
+            prefetch=bool(self.prefetch and not batch_given and cuda), next_in_bwd=bool(next_in_bwd))
 
     def _train_image(self):
         """np.random.choice(i_train) (run_nerf.py:578) from the host generator."""
@@ -752,20 +765,27 @@ class Trainer:
         return out
 
     def _draw_rays(self, i: int, uniforms=None):
-        """The step's rays and targets: the shuffled pool (use_batching) or
-        N_rand pixels of one training image (device sampler, centre crop
-        before precrop_iters).  uniforms = per-ray counts of torch.rand draws
-        on the default generator to make as well ([B, n] each, bitwise
-        torch's: functional.torch_uniform, inside the sampler's launch),
-        returned after rays and target."""
+        """The step's rays and targets: the shuffled pool (use_batching) or N_rand pixels of one
+        training image (device sampler, centre crop before precrop_iters).  uniforms = per-ray counts
+        of torch.rand draws on the default generator to make as well ([B, n] each, bitwise torch's:
+        functional.torch_uniform, inside the sampler's launch), returned after rays and target."""
         if self.use_batching:
             return self._pool_draw(uniforms)
         a, d = self.args, self.data
-        img_i = self._train_image()
-        crop = self.crop if i < a.precrop_iters else (0, 0, d.H, d.W)
-        return HF.sample_rays(d.images[img_i], d.poses[img_i], a.N_rand, d.K, self.near, self.far, crop,
-                              _step_seed(self.seed, self.rank, i), order=self.ray_order,
-                              uniforms=[(a.N_rand, n) for n in uniforms] if uniforms else None, ndc=self.ndc)
+        img_i, crop, seed = self._image_draw(i)
+        return HF.sample_rays(d.images[img_i], d.poses[img_i], a.N_rand, d.K, self.near, self.far, crop, seed,
+                              order=self.ray_order, ndc=self.ndc,
+                              uniforms=[(a.N_rand, n) for n in uniforms] if uniforms else None)
+
+    def _image_draw(self, i: int):
+        """The host half of step i's per-image draw: (training image, crop window, the device sampler's seed)."""
+        d = self.data
+        crop = self.crop if i < self.args.precrop_iters else (0, 0, d.H, d.W)
+        return self._train_image(), crop, _step_seed(self.seed, self.rank, i)
+
+    def _tv_on(self, i: int) -> bool:
+        """Whether step i carries the TV term (rank 0, i <= tv_until)."""
+        return self.args.tv_loss_weight > 0 and self.rank == 0 and i <= self.args.tv_until
 
     def sample_rays(self, i: int):
         """run_nerf.py:576-605 on the device: one image, N_rand pixels."""
@@ -788,34 +808,30 @@ class Trainer:
         mse = img2mse(rgb, target)
         mse0 = img2mse(extras["rgb0"], target) if "rgb0" in extras else None
         sp = extras["sparsity_loss"].sum() + extras["sparsity_loss0"].sum()
-        tv = None
-        if a.tv_loss_weight > 0 and self.rank == 0 and i <= a.tv_until:
-            tv = tv_loss_levels(self.embed_fn, generator=self.cpu_gen).sum()
+        tv = tv_loss_levels(self.embed_fn, generator=self.cpu_gen).sum() if self._tv_on(i) else None
         loss = dp_loss(mse, mse0, sp, self.world, a.sparse_loss_weight, tv, a.tv_loss_weight)
         return loss, mse
 
     def _live_rows(self):
-        if not hasattr(self, "_live"):
+        if self._live is False:
             e = self.embed_fn
             lv = live_rows(e.resolutions, e.log2_hashmap_size)
             self._live = None if lv is None else (lv[0], lv[1].to(self.device))
         return self._live
 
     def _live_mask(self):
-        """train.live_pair_mask on the device (built once), or None when
-        Trainer.skip_dead_rows is off."""
+        """train.live_pair_mask on the device (built once), or None when Trainer.skip_dead_rows is off."""
         if not self.skip_dead_rows:
             return None
-        if not hasattr(self, "_livem"):
+        if self._livem is False:
             e = self.embed_fn
             lm = live_pair_mask(e.resolutions, e.log2_hashmap_size)
             self._livem = None if lm is None else (lm[0], lm[1].to(self.device))
         return self._livem
 
     def finish_table_grad(self):
-        """Run the backward's deferred owner pass over the bins it has not
-        reduced yet (the segmented DP exchange defers it; see step()), so
-        that table.grad holds the whole table gradient."""
+        """Run the backward's deferred owner pass over the bins it has not reduced yet (StepPlan.owner_defer:
+        the segmented DP exchange's), so that table.grad holds the whole table gradient."""
         st, self._owner_st = self._owner_st, None
         if st is not None:
             HF.render_bwd_owner(st, 0, HF.render_bins(self._cfg, st.rays.shape[0])[0])
@@ -842,17 +858,16 @@ class Trainer:
         if not _fusable(torch.empty(1, 11), nf, nq, kw["N_samples"], kw["N_importance"], nfine):
             raise NotImplementedError("Trainer(mode='explicit') needs the HashNeRF configuration")
         a = self.args
-        self._cfg = HF.make_render_cfg(self.embed_fn.grid(), bool(kw.get("white_bkgd", False)),
-                                       bool(kw.get("lindisp", False)), kw.get("perturb", 0.) > 0.,
-                                       n_importance=kw["N_importance"], dense_bwd=self.dense_bwd)
-        if kw["N_importance"] != 128 and HF.L.lib().hn_render_scatter_mode(self._cfg, a.N_rand) != 2:
+        cfg = HF.make_render_cfg(self.embed_fn.grid(), bool(kw.get("white_bkgd", False)),
+                                 bool(kw.get("lindisp", False)), kw.get("perturb", 0.) > 0.,
+                                 n_importance=kw["N_importance"], dense_bwd=self.dense_bwd)
+        binned = HF.L.lib().hn_render_scatter_mode(cfg, a.N_rand) == 2
+        if kw["N_importance"] != 128 and not binned:
             raise NotImplementedError("Trainer(mode='explicit') at N_importance = 64 needs the binned backward "
                                       "schedule (hn_render_scatter_mode == 2 for this grid and N_rand)")
         self._t_vals = _linspace_cached(kw["N_samples"], self.device)
         self._ws = nf.weights() + nfine.weights()
         table = self.embed_fn.table
-        # world > 1 (explicit mode): the table's exchange + RAdam step sharded over
-        # the ranks (ShardedTableStep); the backward writes into its buffer
         if self._xchg is not None and self._xchg.stale:
             # a rebuilt exchange seeds its shards from optimizer.state, which is
             # out of date while the previous exchange's moments are newer
@@ -860,9 +875,9 @@ class Trainer:
                                "call sync_optimizer_state() on every rank before rebuilding the step")
         self._xchg = None
         if self.world > 1 and self.dp_sharded:
-            # the moments continue from the optimizer's (a resumed run's
-            # checkpoint, or an earlier setup's gathered state)
-            nb, shift = HF.render_bins(self._cfg, a.N_rand)
+            # the table's exchange + RAdam step sharded over the ranks; the backward writes into its buffer.  The
+            # moments continue from the optimizer's (a resumed run's checkpoint, or an earlier setup's gathered state)
+            nb, shift = HF.render_bins(cfg, a.N_rand)
             self._xchg = ShardedTableStep(table, self._live_rows(), self.rank, self.world,
                                           state=self.optimizer.state.get(table),
                                           bins=(nb, shift) if nb else None, n_chunks=self.dp_chunks)
@@ -871,23 +886,20 @@ class Trainer:
         else:
             self._gtable = torch.zeros_like(table)
         self._pk = None          # (re)setup: the weights may have been replaced
-        self._binned = HF.L.lib().hn_render_scatter_mode(self._cfg, a.N_rand) == 2
-        # the ten MLP gradients: views of ONE flat buffer (the DP exchange
-        # all-reduces it in place, no concatenation or copy-back)
+        # the ten MLP gradients: views of ONE flat buffer (the DP exchange all-reduces it in place, no copy-back)
         self._gws = HF.zeros_like_all(self._ws)
         self._gflat = self._gws[0]._base
         self._one = torch.ones((), device=self.device)
         self._gtv = None
-        self._grads = True
+        self._cfg, self._binned = cfg, binned    # last: a setup that raised is run again
 
     def draw_batch(self, i: Optional[int] = None):
-        """The random inputs of step i (default: the next step, global_step + 1), drawn the way run_nerf.py:576-605 and
-        render_rays draw them: the image (host generator), N_rand pixels
-        without replacement (device sampler, centre crop before
-        precrop_iters), the stratified jitter t_rand and importance uniforms u
-        (device RNG), and the TV cubes + min vertices (rank 0, i <= tv_until).
+        """The random inputs of step i (default: the next step, global_step + 1), drawn the way
+        run_nerf.py:576-605 and render_rays draw them: the image (host generator), N_rand pixels
+        without replacement (device sampler, centre crop before precrop_iters), the stratified jitter
+        t_rand and importance uniforms u (device RNG), and the TV cubes + min vertices (_tv_on(i)).
         Returns a dict rays [B, 11], target [B, 3], t_rand, u, tv (or None)."""
-        a, d, kw = self.args, self.data, self.kw_train
+        kw = self.kw_train
         i = self.global_step + 1 if i is None else i
         if self._nb is not None:
             # the batch the previous step's backward drew (fuse_next_batch)
@@ -902,10 +914,9 @@ class Trainer:
             warnings.warn(f"Trainer.draw_batch({i}): dropping the batch of step {j}, drawn ahead before the "
                           "trainer's settings left fuse_next_batch's mode (its random numbers stay consumed)")
         perturb = kw.get("perturb", 0.) > 0.
-        # two draws in render_rays' order (run_nerf_helpers.py:528, then :276 via :548): the
-        # autograd and reference-path modes draw them the same way, so all
-        # modes see the same numbers for the same device RNG state.  On the
-        # device they are torch.rand restated bit for bit and made in the
+        # two draws in render_rays' order (run_nerf_helpers.py:528, then :276 via :548): the autograd and
+        # reference-path modes draw them the same way, so all modes see the same numbers for the same
+        # device RNG state.  On the device they are torch.rand restated bit for bit and made in the
         # sampler's first launch (one launch instead of three)
         if perturb and self.device.type == "cuda":
             rays, target, t_rand, u = self._draw_rays(i, uniforms=(kw["N_samples"], kw["N_importance"]))
@@ -919,32 +930,21 @@ class Trainer:
 
     def _draw_tv(self, i: int):
         """Step i's TV cubes + min vertices (rank 0, i <= tv_until), or None."""
-        a = self.args
-        if a.tv_loss_weight > 0 and self.rank == 0 and i <= a.tv_until:
-            return draw_tv_cubes(self.embed_fn.n_levels, self.embed_fn.base_resolution,
-                                 self.embed_fn.finest_resolution, self.cpu_gen)
-        return None
+        e = self.embed_fn
+        return (draw_tv_cubes(e.n_levels, e.base_resolution, e.finest_resolution, self.cpu_gen)
+                if self._tv_on(i) else None)
 
     def _fuses_next_batch(self):
-        """Whether a self-driven step draws the next batch inside its render
-        backward (fuse_next_batch): the backward must run the lists and
-        placement launches and the owner pass itself (one GPU, binned
-        schedule, fused table step), and the batch must be the per-image
-        Morton sampler's with its uniform draws."""
-        return bool(self.fuse_next_batch and not self.prefetch and self.mode == "explicit" and self.world == 1
-                    and self.device.type == "cuda" and not self.use_batching and self.ray_order == 1
-                    and self._binned and self.fuse_table_step and self.kw_train.get("perturb", 0.) > 0.)
+        """Whether a self-driven step draws the next batch inside its render backward (StepPlan.next_in_bwd)."""
+        return self._plan(self_driven=True).next_in_bwd
 
     def _draw_next(self, i: int):
-        """draw_batch(i) with the device half left to a render backward: the
-        host half in draw_batch's order (image, step seed, the default
-        generator's philox offsets, TV cubes).  Returns the batch, whose
-        tensors that backward fills, and the job for render_bwd."""
+        """draw_batch(i) with the device half left to a render backward: the host half in draw_batch's
+        order (image, step seed, the default generator's philox offsets, TV cubes).  Returns the
+        batch, whose tensors that backward fills, and the job for render_bwd."""
         a, d, kw = self.args, self.data, self.kw_train
-        img_i = self._train_image()
-        crop = self.crop if i < a.precrop_iters else (0, 0, d.H, d.W)
-        nb = HF.next_batch(d.images[img_i], d.poses[img_i], a.N_rand, d.K, self.near, self.far, crop,
-                           _step_seed(self.seed, self.rank, i),
+        img_i, crop, seed = self._image_draw(i)
+        nb = HF.next_batch(d.images[img_i], d.poses[img_i], a.N_rand, d.K, self.near, self.far, crop, seed,
                            uniforms=[(a.N_rand, kw["N_samples"]), (a.N_rand, kw["N_importance"])], ndc=self.ndc)
         rays, target, t_rand, u = nb.out
         return dict(rays=rays, target=target, t_rand=t_rand, u=u, tv=self._draw_tv(i)), nb
@@ -978,111 +978,113 @@ class Trainer:
         return pf[1]
 
     def _fused_forward_backward(self, i: int, batch=None, self_driven=False):
-        a = self.args
-        if self._grads is None:
+        """Explicit mode's forward and backward of step i -> (loss, mse), the gradients left in .grad."""
+        if self._cfg is None:
             self._fused_setup()
-        pf = self.prefetch and batch is None and self.device.type == "cuda"
-        if pf:
+        plan = self._plan(batch is not None, self_driven)
+        if plan.prefetch:
             batch = self._take_prefetched(i)
         if batch is None:
             batch = self.draw_batch(i)
-        rays, target, t_rand, u = batch["rays"], batch["target"], batch["t_rand"], batch["u"]
-        table = self.embed_fn.table
-        if rays.shape[0] == 0:
-            return self._empty_rank_grads(batch)
-        tv = mv = cubes = None
+        if batch["rays"].shape[0] == 0:
+            return self._empty_rank_grads(batch, plan)
+        out, st, tv = self._forward(batch, plan)
+        if plan.prefetch:
+            self._prefetch(i + 1)
+        lo, grads, loss, g_tv = self._loss_inputs(out, batch["target"], None if tv is None else tv[0], plan)
+        # the TV term's table gradient joins the render backward (owner-pass records, or added to the stored one)
+        tvb = None if tv is None else (tv[1], tv[2], g_tv)
+        if plan.table_in_owner:
+            self._set_grads(self._backward_in_owner(i, st, grads, loss, tvb, plan))
+        else:
+            self._set_grads(self._backward_stored(st, grads, loss, tvb, plan))
+        return lo[0], lo[1]
+
+    def _forward(self, batch, plan: StepPlan):
+        """The TV forward (a batch with cubes), then the fused render forward.  Returns (outputs,
+        state for the backward, (TV per level, min vertices, cubes) or None)."""
+        a, kw, table = self.args, self.kw_train, self.embed_fn.table
+        rays, target = batch["rays"], batch["target"]
+        tv = None
         if batch["tv"] is not None:
             cubes, mv0 = batch["tv"]
-            tv, mv = HF.tv_fwd(table, mv0, cubes, self.embed_fn.log2_hashmap_size)
-        consts = (self.world, a.sparse_loss_weight, a.tv_loss_weight)
+            tv = (*HF.tv_fwd(table, mv0, cubes, self.embed_fn.log2_hashmap_size), cubes)
         nb = HF.L.lib().hn_render_workspace_bytes(self._cfg, rays.shape[0])
         if self._rws is None or self._rws.numel() < nb:
             self._rws, self._pk = torch.empty(nb, dtype=torch.uint8, device=self.device), None
-        # the colour net of tiles without any density is skipped (the trainer never
-        # returns raw rgb; with dense_bwd everything is computed, for the A/B) --
-        # where the binned backward follows: the float-atomic one loads every tile
-        # one GPU, binned backward, loss formed in the backward: the targets are
-        # known before the forward, so each ray's forward wave runs the loss's
-        # composite backward itself (d raw and the marks left in the workspace)
-        # and the backward launches no pre-pass
-        fold = self.fuse_prepass and self.fuse_loss and self._binned and self.world == 1
         # raw_noise_std (the LLFF configurations train with 1.0): render_rays' two
         # randn draws (run_nerf_helpers.py:599-606), coarse then fine
         noise_c = noise_f = None
-        std = float(self.kw_train.get("raw_noise_std", 0.) or 0.)
+        std = float(kw.get("raw_noise_std", 0.) or 0.)
         if std > 0.:
-            kw = self.kw_train
             noise_c = torch.randn((rays.shape[0], kw["N_samples"]), device=self.device) * std
             noise_f = torch.randn((rays.shape[0], kw["N_samples"] + kw["N_importance"]), device=self.device) * std
-        out, st = HF.render_fwd(self._cfg, rays, self._t_vals, t_rand, u, noise_c, noise_f, table, self._ws, True,
-                                wsb=self._rws, weights_packed=self._pk is not None and self._pk == self._pack_key(),
-                                skip_dead_color=(not self._cfg.dense_bwd) and self._binned,
+        # skip_dead_color: the trainer never returns raw rgb (the float-atomic backward loads every tile).
+        # loss: the targets are known before the forward, so each ray's wave leaves d raw and the marks
+        out, st = HF.render_fwd(self._cfg, rays, self._t_vals, batch["t_rand"], batch["u"], noise_c, noise_f, table,
+                                self._ws, True, wsb=self._rws, skip_dead_color=plan.skip_dead_color,
+                                weights_packed=self._pk is not None and self._pk == self._pack_key(),
                                 loss=dict(target=target, world=self.world, sparse_w=a.sparse_loss_weight)
-                                if fold else None)
+                                if plan.fold_prepass else None)
         self._pk = None
-        if pf:
-            self._prefetch(i + 1)
-        loss = None
-        if self.fuse_loss:
-            # the loss formed by the backward's composite pre-pass (ABI 13):
-            # its rgb / entropy gradients computed where they are used, its
-            # value by one workgroup -- no hn_loss_fwd_bwd launch
+        return out, st, tv
+
+    def _loss_inputs(self, out, target, tv, plan: StepPlan):
+        """What the render backward takes of the loss -> (lo, grads, loss, g_tv): lo[0], lo[1] the loss
+        and MSE (written by the backward with fuse_loss), grads the upstream gradients or {} where
+        ``loss`` has the backward form them, g_tv = d loss / d tv per level."""
+        a = self.args
+        if plan.fuse_loss:
+            # (ABI 13) its rgb / entropy gradients computed where they are used, its value by one workgroup
             lo = torch.empty(4, dtype=torch.float32, device=self.device)
             loss = dict(target=target, rgb=out["rgb"], rgb0=out["rgb0"], sparsity=out["sparsity"],
                         sparsity0=out["sparsity0"], tv=tv, world=self.world, sparse_w=a.sparse_loss_weight,
                         tv_w=a.tv_loss_weight, out=lo)
-            grads = {}
             # d loss / d tv_l = g * tv_w (g = 1, hn_loss_bwd's): a constant vector
             g_tv = None
             if tv is not None:
                 if self._gtv is None or self._gtv.shape != tv.shape:
                     self._gtv = torch.full_like(tv, a.tv_loss_weight)
                 g_tv = self._gtv
-        else:
-            # loss value and its input gradients in one launch (the gradients do
-            # not depend on the value)
-            lo, (g_rgb, g_rgb0, g_sp, g_sp0, g_tv) = HF.loss_fwd_bwd(
-                out["rgb"], out["rgb0"], target, out["sparsity"], out["sparsity0"], tv, *consts, self._one)
-            grads = dict(g_rgb=g_rgb, g_sparsity=g_sp, g_rgb0=g_rgb0, g_sparsity0=g_sp0)
-        # the ten MLP grads (one flat buffer) are written, not accumulated:
-        # no zero fill
-        # the TV term's table gradient joins the render backward (records of
-        # the binned owner pass, or added to the stored gradient)
-        tvb = None if tv is None else (mv, cubes, g_tv)
-        if self.fuse_table_step and self.world == 1 and self._binned:
-            # one GPU: the table gradient (render + TV) is complete where the
-            # binned owner pass forms it, so the table's RAdam step runs there
-            # (run_nerf.py:642 for the embedding group) and the gradient is
-            # never stored; optimizer.step() then updates the MLP groups only
-            # the MLP groups' steps likewise, where the slab reduction forms
-            # their gradients (optimizer.step() then has nothing left)
-            mstep = [self.optimizer.take_step(p) for p in self._ws] if self.fuse_mlp_step else None
-            # a self-driven loop: batch i + 1 drawn by this backward's lists and
-            # placement launches (fuse_next_batch), into tensors of its own --
-            # this backward still reads step i's target and rays
-            nxt = job = None
-            if self_driven and self._fuses_next_batch():
-                nxt, job = self._draw_next(i + 1)
-            HF.render_bwd(st, grads, None, self._gws, table_step=self.optimizer.take_step(table),
-                          overwrite_mlp=True, tv=tvb, table_live=self._live_mask(), loss=loss, mlp_step=mstep,
-                          repack=mstep is not None, prepass_done=fold, next_batch=job)
-            if nxt is not None:
-                self._nb = (i + 1, nxt)
-            if mstep is not None:
-                self._pk = self._pack_key()   # the workspace holds the stepped weights' copies
-            table.grad = None
-        else:
-            # the render backward writes every table-gradient entry (overwrite:
-            # no zero fill of the 64 MiB buffer), TV included; with a segmented
-            # DP exchange its owner pass runs per segment inside the exchange
-            defer = self._xchg is not None and self._xchg.seg_bins is not None
-            HF.render_bwd(st, grads, self._gtable, self._gws, overwrite=True, overwrite_mlp=True, tv=tvb,
-                          owner_defer=defer, loss=loss, prepass_done=fold)
-            self._owner_st = st if defer else None
-            table.grad = self._gtable
+            return lo, {}, loss, g_tv
+        # loss value and its input gradients in one launch (the gradients do not depend on the value)
+        lo, (g_rgb, g_rgb0, g_sp, g_sp0, g_tv) = HF.loss_fwd_bwd(
+            out["rgb"], out["rgb0"], target, out["sparsity"], out["sparsity0"], tv, self.world,
+            a.sparse_loss_weight, a.tv_loss_weight, self._one)
+        return lo, dict(g_rgb=g_rgb, g_sparsity=g_sp, g_rgb0=g_rgb0, g_sparsity0=g_sp0), None, g_tv
+
+    def _backward_in_owner(self, i, st, grads, loss, tvb, plan: StepPlan):
+        """The render backward with the optimizer inside it: the table gradient (render + TV) is complete
+        where the owner pass forms it, so the table's RAdam step (run_nerf.py:642) runs there and the gradient
+        is never stored (returns the table's .grad: None); with mlp_in_slab optimizer.step() has nothing left."""
+        mstep = [self.optimizer.take_step(p) for p in self._ws] if plan.mlp_in_slab else None
+        # a self-driven loop: batch i + 1 drawn by this backward's lists and placement launches, into
+        # tensors of its own -- this backward still reads step i's target and rays
+        nxt, job = self._draw_next(i + 1) if plan.next_in_bwd else (None, None)
+        # (the ten MLP grads, one flat buffer, are written, not accumulated: no zero fill)
+        HF.render_bwd(st, grads, None, self._gws, table_step=self.optimizer.take_step(self.embed_fn.table),
+                      overwrite_mlp=True, tv=tvb, table_live=self._live_mask(), loss=loss, mlp_step=mstep,
+                      repack=mstep is not None, prepass_done=plan.fold_prepass, next_batch=job)
+        if nxt is not None:
+            self._nb = (i + 1, nxt)
+        if mstep is not None:
+            self._pk = self._pack_key()   # the workspace holds the stepped weights' copies
+        return None
+
+    def _backward_stored(self, st, grads, loss, tvb, plan: StepPlan):
+        """The render backward into the stored table gradient, which it returns: every entry written
+        (overwrite: no zero fill of the 64 MiB buffer), TV included; with owner_defer the owner pass
+        is left to the segmented DP exchange (_exchange_step)."""
+        HF.render_bwd(st, grads, self._gtable, self._gws, overwrite=True, overwrite_mlp=True, tv=tvb,
+                      owner_defer=plan.owner_defer, loss=loss, prepass_done=plan.fold_prepass)
+        self._owner_st = st if plan.owner_defer else None
+        return self._gtable
+
+    def _set_grads(self, table_grad):
+        """Hand the step's gradients to the parameters' .grad."""
+        self.embed_fn.table.grad = table_grad
         for p, g in zip(self._ws, self._gws):
             p.grad = g
-        return lo[0], lo[1]
 
     def _pack_key(self):
         """What the workspace's packed weights must match: the buffer and
@@ -1098,11 +1100,10 @@ class Trainer:
         way its version counter does not record."""
         self._pk = None
 
-    def _empty_rank_grads(self, batch):
-        """A rank that drew no rays this step (world > 1, use_batching: the
-        short last batch of an epoch holds fewer positions than ranks,
-        run_nerf.py:551-555) still joins the exchange: its gradient is the TV
-        term's alone (rank 0) or zero, its MSE / entropy terms empty."""
+    def _empty_rank_grads(self, batch, plan: StepPlan):
+        """A rank that drew no rays this step (world > 1, use_batching: the short last batch of an
+        epoch holds fewer positions than ranks, run_nerf.py:551-555) still joins the exchange: its
+        gradient is the TV term's alone (rank 0) or zero, its MSE / entropy terms empty."""
         table = self.embed_fn.table
         if self.world == 1:
             raise RuntimeError("Trainer: an empty batch on a single rank")
@@ -1115,30 +1116,70 @@ class Trainer:
             w = self.args.tv_loss_weight
             lo[0] = w * tv.sum()
             g_tv = torch.full_like(tv, w)
-            if self._binned:
+            if plan.binned:
                 # the TV term alone through the binned scatter's records and exact
                 # owner pass (bitwise reproducible, as a rendering rank's TV term)
                 self._rws0 = HF.tv_bwd_records(self._cfg, table, mv, cubes, g_tv, self._gtable,
                                                wsb=self._rws if self._rws is not None else self._rws0)
             else:
                 HF.tv_bwd(table, mv, cubes, self.embed_fn.log2_hashmap_size, g_tv, self._gtable)
-        table.grad = self._gtable
         self._gflat.zero_()
-        for p, g in zip(self._ws, self._gws):
-            p.grad = g
+        self._set_grads(self._gtable)
         return lo[0], lo[1]
+
+    def _module_step(self, i: int):
+        """Forward, loss and loss.backward() of step i through the module API (modes "autograd", "eager")."""
+        a = self.args
+        self.optimizer.zero_grad(set_to_none=True)
+        if self.mode == "autograd":
+            rays, target = self._draw_rays(i)
+            rgb, depth, acc, extras = render_ray_batch(rays, (rays.shape[0],), chunk=a.chunk, retraw=True,
+                                                       **self.kw_train)
+            tv = tv_loss_levels(self.embed_fn, generator=self.cpu_gen) if self._tv_on(i) else None
+            loss, mse, _ = HF.train_loss(rgb, extras.get("rgb0"), target, extras["sparsity_loss"],
+                                         extras.get("sparsity_loss0"), tv, self.world, a.sparse_loss_weight,
+                                         a.tv_loss_weight)
+        else:
+            batch_rays, target = self.sample_rays(i)
+            rgb, depth, acc, extras = render(self.data.H, self.data.W, self.data.K, chunk=a.chunk, rays=batch_rays,
+                                             retraw=True, near=self.near, far=self.far, **self.kw_train)
+            loss, mse = self.loss_fn(rgb, extras, target, i)
+        loss.backward()
+        return loss, mse
+
+    def _exchange_step(self):
+        """The sharded DP step.  The table: RAdam state advanced here (take_step), its exchange and
+        update sharded; the ten MLP gradients (views of one flat buffer) all-reduced in place as one
+        bucket beside the table's reduce-scatter, and their RAdam steps taken in the shard's
+        hn_radam_step launch (one launch for all eleven tensors)."""
+        table = self.embed_fn.table
+        _, _, _, coeffs = self.optimizer.take_step(table)
+        t_mlp = HF.TIMER.begin("xchg_mlp_allreduce")
+        work = dist.all_reduce(self._gflat, async_op=True)
+        mst = [self.optimizer.take_step(p) for p in self._ws]
+        extra = [(p, g, m, v, c) for (p, m, v, c), g in zip(mst, self._gws)]
+
+        def wait_mlp():
+            work.wait()
+            HF.TIMER.end("xchg_mlp_allreduce", t_mlp)
+
+        st, self._owner_st = self._owner_st, None
+        produce = None
+        if st is not None:
+            sb = self._xchg.seg_bins
+            produce = lambda k: HF.render_bwd_owner(st, *sb[k])
+        self._xchg.step(coeffs, produce=produce, extra=extra, pre_step=wait_mlp)
+        table.grad = None
 
     def step(self, i: Optional[int] = None, batch=None):
         """One iteration; ``batch`` (explicit mode) = draw_batch(i) drawn by
         the caller, e.g. to feed the same inputs to a reference path.
 
-        ``i`` is the reference loop's index (run_nerf.py:538-541: ``start + 1``
-        onwards, so 1 on a fresh run, global_step + 1 after a resume); it
-        defaults to exactly that.  The windows follow the reference: the
-        centre crop while i < precrop_iters (steps 1..499), TV while
-        i <= tv_until (1001: the weight is zeroed after the loss of step
-        i > 1000 is formed, run_nerf.py:636-638), and the lr set after the
-        step from the pre-increment global_step (:647-651)."""
+        ``i`` is the reference loop's index (run_nerf.py:538-541: ``start + 1`` onwards, so 1 on a
+        fresh run, global_step + 1 after a resume); it defaults to exactly that.  The windows follow
+        the reference: the centre crop while i < precrop_iters (steps 1..499), TV while i <= tv_until
+        (1001: the weight is zeroed after the loss of step i > 1000 is formed, run_nerf.py:636-638),
+        and the lr set after the step from the pre-increment global_step (:647-651)."""
         a = self.args
         self_driven = i is None and batch is None   # the loop is the trainer's own: fuse_next_batch may draw ahead
         i = self.global_step + 1 if i is None else i
@@ -1147,57 +1188,16 @@ class Trainer:
         if self.mode == "explicit":
             loss, mse = self._fused_forward_backward(i, batch, self_driven)
         else:
-            self.optimizer.zero_grad(set_to_none=True)
-            if self.mode == "autograd":
-                rays, target = self._draw_rays(i)
-                rgb, depth, acc, extras = render_ray_batch(rays, (rays.shape[0],), chunk=a.chunk, retraw=True,
-                                                           **self.kw_train)
-                tv = None
-                if a.tv_loss_weight > 0 and self.rank == 0 and i <= a.tv_until:
-                    tv = tv_loss_levels(self.embed_fn, generator=self.cpu_gen)
-                loss, mse, _ = HF.train_loss(rgb, extras.get("rgb0"), target, extras["sparsity_loss"],
-                                             extras.get("sparsity_loss0"), tv, self.world,
-                                             a.sparse_loss_weight, a.tv_loss_weight)
-            else:
-                batch_rays, target = self.sample_rays(i)
-                rgb, depth, acc, extras = render(self.data.H, self.data.W, self.data.K, chunk=a.chunk,
-                                                 rays=batch_rays, retraw=True, near=self.near, far=self.far,
-                                                 **self.kw_train)
-                loss, mse = self.loss_fn(rgb, extras, target, i)
-            loss.backward()
+            loss, mse = self._module_step(i)
         if self._xchg is not None and self.mode == "explicit":
-            # the table: RAdam state advanced here (take_step), its exchange and
-            # update sharded; the ten MLP gradients (views of one flat buffer)
-            # all-reduced in place as one bucket beside the table's
-            # reduce-scatter, and their RAdam steps taken in the shard's
-            # hn_radam_step launch (one launch for all eleven tensors)
-            table = self.embed_fn.table
-            _, _, _, coeffs = self.optimizer.take_step(table)
-            t_mlp = HF.TIMER.begin("xchg_mlp_allreduce")
-            work = dist.all_reduce(self._gflat, async_op=True)
-            mst = [self.optimizer.take_step(p) for p in self._ws]
-            extra = [(p, g, m, v, c) for (p, m, v, c), g in zip(mst, self._gws)]
-
-            def wait_mlp():
-                work.wait()
-                HF.TIMER.end("xchg_mlp_allreduce", t_mlp)
-
-            st, self._owner_st = self._owner_st, None
-            produce = None
-            if st is not None:
-                sb = self._xchg.seg_bins
-                produce = lambda k: HF.render_bwd_owner(st, *sb[k])
-            self._xchg.step(coeffs, produce=produce, extra=extra, pre_step=wait_mlp)
-            table.grad = None
+            self._exchange_step()
         else:
             self.allreduce_grads()
         self.optimizer.step()
-        decay_steps = a.lrate_decay * 1000
-        new_lr = a.lrate * (0.1 ** (self.global_step / decay_steps))
+        new_lr = a.lrate * (0.1 ** (self.global_step / (a.lrate_decay * 1000)))
         for g in self.optimizer.param_groups:
             g["lr"] = new_lr
         self.global_step += 1
-        if self.fault_check_every and self.global_step % self.fault_check_every == 0 and \
-                self.device.type == "cuda":
+        if self.fault_check_every and self.global_step % self.fault_check_every == 0 and self.device.type == "cuda":
             HF.L.check_device_faults()
         return loss, mse

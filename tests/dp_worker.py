@@ -72,7 +72,7 @@ def train(out_path, sharded, steps, resume_at=0):
         if resume_at and k == resume_at:
             tr.sync_optimizer_state()
             tr.optimizer.state_dict()          # refuses stale moments: must not raise now
-            tr._grads = tr._xchg = None        # the next step rebuilds the exchange from optimizer.state
+            tr._drop_setup()                   # the next step rebuilds the exchange from optimizer.state
         tr.step()
     tr.sync_optimizer_state()
     torch.cuda.synchronize()

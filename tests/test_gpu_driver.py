@@ -443,7 +443,6 @@ def test_zero_gradient_skip_bitwise(hn):
     try:
         for dense in (1, 0, 0):
             # the dense form's forward stores every tile's features (skip_dead_color off)
-            tr._cfg.dense_bwd = dense
             tr.dense_bwd = bool(dense)
             tr._fused_forward_backward(2000, batch)
             torch.cuda.synchronize()
@@ -513,3 +512,50 @@ def test_trainer_atomic_schedule_keeps_every_tile(hn, monkeypatch):
         print("table rel", rel(a[0], b[0]), "NeRFSmall rel", [rel(x, y) for x, y in zip(a[1:], b[1:])])
         assert rel(a[0], b[0]) <= 1e-6
         assert max(rel(x, y) for x, y in zip(a[1:], b[1:])) <= 1e-4
+
+
+def test_trainer_flags_flipped_between_steps(hn):
+    """The step's launches are decided per step from the flags' current
+    values: a trainer that turns fuse_loss, fuse_prepass, fuse_mlp_step,
+    fuse_table_step and fuse_next_batch off one after the other before steps
+    2-6 and all of them on again before step 7 (so the packed weights' key and
+    the batch the previous backward drew cross a change of mode both ways)
+    ends 8 self-driven steps (centre crop through step 2, TV through step 5)
+    with table, both moments and the ten weights bitwise those of a trainer
+    that never touched a flag; the losses agree to 1e-6 (the fused loss sums
+    in another order)."""
+    from hashnerf_pytorch_amd.train import SyntheticBlender, Trainer, default_args
+    data = SyntheticBlender(32, 32, 2, DEV, seed=0)
+    flips = ["fuse_loss", "fuse_prepass", "fuse_mlp_step", "fuse_table_step", "fuse_next_batch"]
+    res = {}
+    for flip in (False, True):
+        args = default_args(N_rand=64, log2_hashmap_size=12, tv_loss_weight=1e-4, tv_until=5,
+                            sparse_loss_weight=1e-3, precrop_iters=3)
+        tr = Trainer(args, data, DEV, seed=3)
+        torch.manual_seed(11)
+        losses = []
+        for i in range(1, 9):
+            if flip and 2 <= i <= 6:
+                assert getattr(tr, flips[i - 2]) is True
+                setattr(tr, flips[i - 2], False)
+            if flip and i == 7:
+                for f in flips:
+                    setattr(tr, f, True)
+            losses.append(float(tr.step()[0]))
+        torch.cuda.synchronize()
+        hn._lib.check_device_faults()
+        # every fusion is in effect at this size, and the last step drew batch 9 ahead
+        assert tr._binned and tr._fuses_next_batch() and tr._nb is not None and tr._nb[0] == 9
+        t = tr.embed_fn.table
+        st = tr.optimizer.state[t]
+        ws = tr.kw_train["network_fn"].weights() + tr.kw_train["network_fine"].weights()
+        res[flip] = (losses, t.detach().clone(), st["exp_avg"].clone(), st["exp_avg_sq"].clone(),
+                     [p.detach().clone() for p in ws])
+    a, b = res[False], res[True]
+    print("losses", a[0], b[0])
+    np.testing.assert_allclose(b[0], a[0], rtol=1e-6)
+    for k in (1, 2, 3):
+        assert torch.equal(a[k], b[k]), k
+    for x, y in zip(a[4], b[4]):
+        assert torch.equal(x, y)
+    assert len(set(a[0])) == 8 and not torch.equal(a[2], torch.zeros_like(a[2]))

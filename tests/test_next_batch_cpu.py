@@ -117,14 +117,17 @@ def test_next_batch_validation_without_gpu(hn):
 
 
 def bare_trainer(hn, **over):
-    """A Trainer with only the attributes its next-batch decision reads (no
-    device, no networks)."""
+    """A Trainer with only the attributes its step plan reads (no device, no
+    networks), at Trainer.__init__'s defaults."""
     from hashnerf_pytorch_amd.train import Trainer
     HF = hn.functional
     tr = Trainer.__new__(Trainer)
     tr.fuse_next_batch, tr.prefetch, tr.mode, tr.world = True, False, "explicit", 1
     tr.device, tr.use_batching, tr.ray_order, tr.fuse_table_step = torch.device("cuda", 0), False, 1, True
     tr.kw_train = dict(perturb=1.0)
+    tr.skip_dead_rows = tr.dp_sharded = tr.fuse_mlp_step = tr.fuse_loss = tr.fuse_prepass = True
+    tr._cfg = tr._xchg = None
+    tr.dp_chunks, tr.dense_bwd = 1, False
     scatter = over.pop("scatter", "binned")
     emb = hn.HashEmbedder(BOX, log2_hashmap_size=14, finest_resolution=64)
     cfg = HF.make_render_cfg(emb.grid(), True, False, True, scatter=scatter)
