@@ -326,35 +326,8 @@ HN_DEV void b1_unit(const B1K& k, int64_t ray, int part, float* X, DW& dw, WRing
   float4 dr[2];
 #pragma unroll
   for (int t = 0; t < 2; ++t) dr[t] = *reinterpret_cast<const float4*>(drs + 128 * t);
-  float sh8[8], shx8[8];
-  ray_sh(r, h, sh8, shx8);
-  {   // sh part of color_net.0's input: features 8h .. 8h + 7 of the [sh16 | sigma | geo15] image
-    const SP<2> sp = splitn<2>([&](int j) { return shx8[j]; });
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const u32x4 w = __builtin_bit_cast(u32x4, sp.p[q]);
-      put_quad(reinterpret_cast<char*>(X), kBC0in, q, p, 2 * h, w[0], w[1]);
-      put_quad(reinterpret_cast<char*>(X), kBC0in, q, p, 2 * h + 1, w[2], w[3]);
-    }
-  }
   const float* P = opaque_ptr(fine ? k.Pf : k.Pc);
-  // color_net.0 applied to the sh part: the same for every point of the ray
-  // (and bit-identical to starting each point's chain with it)
-  C0Sh c0sh;
-  {
-    float* cl = X + kC0shF;
-#pragma unroll
-    for (int ob = 0; ob < 2; ++ob) {
-      const f32x16 v = gemm<R_F2S>(P, ob, zero16(), lane, [&](int s) { return sh8[s]; });
-      if (p == 0)   // every point's column holds the same rows: lanes 0 and 32 store them
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<f32x4*>(cl + 32 * ob + row_of(4 * g, h)) =
-              f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
-    }
-    lds_fence_wave();
-    c0sh.lds = cl;
-  }
+  const C0Sh c0sh = c0sh_setup<false>(P, r, X, lane);
   const int ctile = (fine ? kSc / 32 : 0) + tile0;
   float zq[2] = {0.f, 0.f};
   int srcq[2] = {0, 0};

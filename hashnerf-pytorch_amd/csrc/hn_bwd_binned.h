@@ -377,32 +377,9 @@ HN_DEV void b1_groups(const B1K& k, int ca, int cb, bool fine, float* X, DW& dw,
   float4 dr = *reinterpret_cast<const float4*>(k.draw + ((size_t)ray * (kSc + kSf) + (fine ? kSc : 0) + i) * 4);
   if (none) dr = make_float4(0.f, 0.f, 0.f, 0.f);
   const float* P = opaque_ptr(fine ? k.Pf : k.Pc);
-  C0Sh c0sh;
-  {
-    Ray r;
-    load_ray(k.rays, ray, r);
-    float sh8[8], shx8[8];
-    ray_sh(r, h, sh8, shx8);
-    const SP<2> sp = splitn<2>([&](int j) { return shx8[j]; });
-#pragma unroll
-    for (int q = 0; q < 2; ++q) {
-      const u32x4 w = __builtin_bit_cast(u32x4, sp.p[q]);
-      put_quad(reinterpret_cast<char*>(X), kBC0in, q, p, 2 * h, w[0], w[1]);
-      put_quad(reinterpret_cast<char*>(X), kBC0in, q, p, 2 * h + 1, w[2], w[3]);
-    }
-    float* cl = X + kC0shF;
-#pragma unroll
-    for (int ob = 0; ob < 2; ++ob) {
-      const f32x16 v = gemm<R_F2S>(P, ob, zero16(), lane, [&](int s) { return sh8[s]; });
-      if ((p & 15) == 0)   // columns 0 and 16: the two groups' rays
-#pragma unroll
-        for (int g = 0; g < 4; ++g)
-          *reinterpret_cast<f32x4*>(cl + 64 * (p >> 4) + 32 * ob + row_of(4 * g, h)) =
-              f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
-    }
-    lds_fence_wave();
-    c0sh.lds = cl + 64 * (p >> 4);
-  }
+  Ray r;
+  load_ray(k.rays, ray, r);
+  const C0Sh c0sh = c0sh_setup<true>(P, r, X, lane);
   // the point's place in the saved tiles: tile (pass offset + i / 32), lane (i % 32) + 32 h
   const int ctile = (fine ? kSc / 32 : 0) + (i >> 5), pl = (i & 31) + 32 * h;
   const float* fb = k.feat + (size_t)ray * HN_RENDER_FEAT_PER_RAY;

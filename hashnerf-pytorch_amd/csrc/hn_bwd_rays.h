@@ -41,37 +41,6 @@ struct RaysK {
   float* part;          // [B][kTilesPerRay][kRayPart]
 };
 
-// The data path of one tile's MLP backward (mlp_bwd_tile's GEMMs in its
-// order, without dW): d raw -> d feature [32 per point, the feature tile's D
-// layout] and d sh [16 per point: registers 0..7 = rows row_of(r, h)].  The
-// ReLU decisions are the forward's own, from its saved mask words sm = [h0 |
-// c0 | c1] (mask_bits), so no activation is recomputed and no feature read.
-HN_DEV void mlp_bwd_data_tile(const float* __restrict__ P, const uint32_t (&sm)[3], float4 dr, f32x16& dfeat,
-                              f32x16& dsh, int lane) {
-  const int h = lane >> 5;
-  const float dy2[2] = {h ? dr.y : dr.x, h ? 0.f : dr.z};
-  f32x16 dc1[2], dc0[2], dh0[2];
-#pragma unroll
-  for (int ob = 0; ob < 2; ++ob) {
-    dc1[ob] = gemm<R_B4>(P, ob, zero16(), lane, [&](int s) { return s < 2 ? dy2[s] : 0.f; });
-    mask_bits(dc1[ob], sm[2], ob);
-  }
-#pragma unroll
-  for (int ob = 0; ob < 2; ++ob) {
-    dc0[ob] = gemm<R_B3>(P, ob, zero16(), lane, [&](int s) { return dc1[s >> 4][s & 15]; });
-    mask_bits(dc0[ob], sm[1], ob);
-  }
-  f32x16 ds1 = gemm<R_B2G>(P, 0, zero16(), lane, [&](int s) { return dc0[s >> 4][s & 15]; });
-  if (h == 0) ds1[0] = dr.w;                    // row 0 = sigma (A row 0 is zero)
-  dsh = gemm<R_B2S>(P, 0, zero16(), lane, [&](int s) { return dc0[s >> 4][s & 15]; });
-#pragma unroll
-  for (int ob = 0; ob < 2; ++ob) {
-    dh0[ob] = gemm<R_B1>(P, ob, zero16(), lane, [&](int s) { return ds1[s]; });
-    mask_bits(dh0[ob], sm[0], ob);
-  }
-  dfeat = gemm<R_B0>(P, 0, zero16(), lane, [&](int s) { return dh0[s >> 4][s & 15]; });
-}
-
 // v summed over the lanes l ^ 1 .. l ^ top (a butterfly of ds_bpermute moves:
 // the same order on every launch)
 template <int TOP>
@@ -104,8 +73,15 @@ __global__ __launch_bounds__(64 * kRayWaves) void render_bwd_rays_kernel(RaysK k
   }
   uint32_t sm[3];
   load_masks(k.feat, ray, tile, lane, sm);
+  // The data path of the tile's MLP backward (mlp_bwd_tile, nothing at its dW
+  // points): d raw -> d feature [32 per point, the feature tile's D layout] and
+  // d sh [16 per point].  The ReLU decisions are the forward's own, from its
+  // saved mask words sm = [h0 | c0 | c1], so no activation is recomputed and no
+  // feature read.
   f32x16 dfeat, dsh;
-  mlp_bwd_data_tile(opaque_ptr(fine ? k.Pf : k.Pc), sm, dr, dfeat, dsh, lane);
+  mlp_bwd_tile(
+      opaque_ptr(fine ? k.Pf : k.Pc), dr, [&](f32x16& v, int l, int ob) { mask_bits(v, sm[l], ob); },
+      [](auto, const f32x16*) {}, dfeat, &dsh, lane);
   // the point, and its d x over this lane half's eight levels
   Ray r;
   load_ray(k.rays, ray, r);

@@ -453,38 +453,22 @@ HN_DEV bf16x8 as_bf16x8(const f32x4 v) { return __builtin_bit_cast(bf16x8, v); }
 HN_DEV f32x16 mfma_bf(const bf16x8 a, const bf16x8 b, f32x16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_bf16(a, b, c, 0, 0, 0);
 }
-// acc += A . B, both as NS parts; the smallest products first
+// c[k] += A[k] . B for NB blocks that share one split of B, all as NS parts;
+// the smallest products first, each product for block 0, then block 1 (the
+// chains interleaved: every accumulator sees the products in the same order)
+template <int NS, int NB>
+HN_DEV void mfma_split(const SP<NS>* a, const SP<NS>& b, f32x16* c) {
+  static_assert(NS == 2 || NS == 3, "parts");
+  constexpr int qa[6] = {2, 0, 1, 1, 0, 0}, qb[6] = {0, 2, 1, 0, 1, 0};   // NS = 2: the last three
+#pragma unroll
+  for (int i = 6 - NS * (NS + 1) / 2; i < 6; ++i)
+#pragma unroll
+    for (int k = 0; k < NB; ++k) c[k] = mfma_bf(a[k].p[qa[i]], b.p[qb[i]], c[k]);
+}
 template <int NS>
 HN_DEV f32x16 mfma_split(const SP<NS>& a, const SP<NS>& b, f32x16 c) {
-  static_assert(NS == 2 || NS == 3, "parts");
-  if constexpr (NS == 3) {
-    c = mfma_bf(a.p[2], b.p[0], c);
-    c = mfma_bf(a.p[0], b.p[2], c);
-    c = mfma_bf(a.p[1], b.p[1], c);
-  }
-  c = mfma_bf(a.p[1], b.p[0], c);
-  c = mfma_bf(a.p[0], b.p[1], c);
-  return mfma_bf(a.p[0], b.p[0], c);
-}
-// c0 += A0 . B, c1 += A1 . B (one split of B, the two chains interleaved;
-// each accumulator sees the products in mfma_split's order)
-template <int NS>
-HN_DEV void mfma_split2(const SP<NS>& a0, const SP<NS>& a1, const SP<NS>& b, f32x16& c0, f32x16& c1) {
-  static_assert(NS == 2 || NS == 3, "parts");
-  if constexpr (NS == 3) {
-    c0 = mfma_bf(a0.p[2], b.p[0], c0);
-    c1 = mfma_bf(a1.p[2], b.p[0], c1);
-    c0 = mfma_bf(a0.p[0], b.p[2], c0);
-    c1 = mfma_bf(a1.p[0], b.p[2], c1);
-    c0 = mfma_bf(a0.p[1], b.p[1], c0);
-    c1 = mfma_bf(a1.p[1], b.p[1], c1);
-  }
-  c0 = mfma_bf(a0.p[1], b.p[0], c0);
-  c1 = mfma_bf(a1.p[1], b.p[0], c1);
-  c0 = mfma_bf(a0.p[0], b.p[1], c0);
-  c1 = mfma_bf(a1.p[0], b.p[1], c1);
-  c0 = mfma_bf(a0.p[0], b.p[0], c0);
-  c1 = mfma_bf(a1.p[0], b.p[0], c1);
+  mfma_split<NS, 1>(&a, b, &c);
+  return c;
 }
 // Level handled by register pair (2m, 2m+1) of lane half h in the 32-feature
 // tile layout: feature ROW(2m,h) = 2 * lev(m,h).

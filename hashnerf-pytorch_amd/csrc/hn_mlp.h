@@ -324,7 +324,7 @@ HN_DEV void mlp_fwd_tile_src(const Src& P, const f32x16& feat, C0Init&& c0init, 
   a.m[0] = a.m[1] = a.m[2] = 0u;
   // sigma_net.0: 32 -> 64, ReLU
   // (Both output blocks of a GEMM sharing one B split per chunk, as the
-  // backward's gemm_w2 does, measured slower here: render_fwd_kernel 0.300 ->
+  // backward's paired gemm_w does, measured slower here: render_fwd_kernel 0.300 ->
   // 0.307 ms, more spills at 4 waves per SIMD; r04c.)
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob) {
@@ -453,95 +453,54 @@ HN_DEV void wgrad_accum(const float* Tdy, const float* Tx, float* Wacc, int base
   __builtin_amdgcn_sched_barrier(0);
 }
 
-// Backward of one tile given the recomputed activations.
-//   dy2[2]: B operand of the rgb gradient (lane half 0: ch 0, 2; half 1: ch 1, 0)
-//   dsig  : d sigma (valid on lane half 0)
-//   rgbg  : the point's 3 rgb grads (for the dW_c2 staging; lane half 0)
-//   shx8  : sh[8h .. 8h+7] of the point (dW_c0 staging)
-//   T     : this wave's 2 transpose buffers; Wacc: the workgroup's dW accumulator
-//   dsh   : if non-null, also return d sh (standalone NeRFSmall backward)
-// (The same GEMM chain -- R_B4, R_B3, R_B2G / R_B2S, R_B1, R_B0 with the ReLU
-// masks between them -- is written out twice more: b1_tile (hn_mlp_bwd.h, on
-// the weight ring, with the dW products) and mlp_bwd_data_tile (hn_bwd_rays.h,
-// the data path alone on saved mask words).  A change of the regions' layout
-// or order is made in all three.)
-HN_DEV void mlp_bwd_tile(const float* __restrict__ P, const f32x16& feat, const float shx8[8],
-                         MlpAct& a, const float dy2[2], float dsig, const float rgbg[3], float* T,
-                         float* Wacc, f32x16& dfeat, f32x16* dsh, int lane) {
-  const int p = lane & 31, h = lane >> 5;
-  float* Tdy = T;
-  float* Tx = T + kTBuf;
-  // ---- color_net.2 ----
-  if (h == 0) {
-    Tdy[p * kTS + 0] = rgbg[0];
-    Tdy[p * kTS + 1] = rgbg[1];
-    Tdy[p * kTS + 2] = rgbg[2];
-  }
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-    stage_tile(Tx, a.c1[kb], lane);
-    wgrad_accum(Tdy, Tx, Wacc, W_C2, 64, 0, 3, kb * 32, 64, lane);
-  }
-  f32x16 dc1[2];
+// Backward of one tile on register operands: the GEMM chain R_B4, R_B3, R_B2G
+// (/ R_B2S), R_B1, R_B0 with the ReLU decisions between them.
+//   dr    : the point's d raw (rgb grads, d sigma; read on its lane half: the
+//           rgb B operand is ch 0, 2 on half 0 and ch 1 on half 1)
+//   relu(g, l, ob): zero block ob of layer l's gradient where its ReLU was off
+//           (l = 0 h0, 1 c0, 2 c1): from an activation (mask16) or a saved
+//           mask word (mask_bits, hn_mlp_bwd.h)
+//   wgrad(l, g): layer l's dW point (l a std::integral_constant: 4 color_net.2
+//           .. 0 sigma_net.0, so each layer's body is its own instantiation), g =
+//           the layer's output gradient blocks (null at 4: d raw itself); what
+//           runs there is the caller's -- mlp_bwd_kernel stages the operands
+//           and accumulates, the ray gradients' data path does nothing
+//   dsh   : if non-null, also return d sh (registers 0..7 = rows row_of(r, h))
+// The same chain is stated once more, in b1_tile (hn_mlp_bwd.h): there the
+// weight fragments come off the ring, every GEMM stages its B operand as a dW
+// image and runs the previous layer's dW products in its own gaps, which is
+// what that statement exists for.  A change of the regions' layout or order
+// is made in both.
+template <typename Relu, typename WGrad>
+HN_DEV void mlp_bwd_tile(const float* __restrict__ P, float4 dr, Relu&& relu, WGrad&& wgrad, f32x16& dfeat,
+                         f32x16* dsh, int lane) {
+  const int h = lane >> 5;
+  const float dy2[2] = {h ? dr.y : dr.x, h ? 0.f : dr.z};
+  f32x16 dc1[2], dc0[2], dh0[2];
+  wgrad(std::integral_constant<int, 4>{}, nullptr);
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob) {
     dc1[ob] = gemm<R_B4>(P, ob, zero16(), lane, [&](int s) { return s < 2 ? dy2[s] : 0.f; });
-    mask16(dc1[ob], a.c1[ob]);
+    relu(dc1[ob], 2, ob);
   }
-  // ---- color_net.1 ----
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb) {
-    stage_tile(Tdy, dc1[nb], lane);
-#pragma unroll
-    for (int kk = 0; kk < 2; ++kk) {
-      const int kb = nb ? 1 - kk : kk;   // reuse the staged X block across nb
-      if (!(nb == 1 && kk == 0)) stage_tile(Tx, a.c0[kb], lane);
-      wgrad_accum(Tdy, Tx, Wacc, W_C1, 64, nb * 32, 64, kb * 32, 64, lane);
-    }
-  }
-  f32x16 dc0[2];
+  wgrad(std::integral_constant<int, 3>{}, dc1);
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob) {
     dc0[ob] = gemm<R_B3>(P, ob, zero16(), lane, [&](int s) { return dc1[s >> 4][s & 15]; });
-    mask16(dc0[ob], a.c0[ob]);
+    relu(dc0[ob], 1, ob);
   }
-  // ---- color_net.0: X = [sh16 | geo15] ----
-#pragma unroll
-  for (int j = 0; j < 8; ++j) Tx[p * kTS + 8 * h + j] = shx8[j];
-#pragma unroll
-  for (int r = 0; r < 8; ++r) {
-    const int row = row_of(r, h);               // s1 rows 0..15
-    if (row >= 1) Tx[p * kTS + 15 + row] = a.s1[r];
-  }
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb) {
-    stage_tile(Tdy, dc0[nb], lane);
-    wgrad_accum(Tdy, Tx, Wacc, W_C0, 31, nb * 32, 64, 0, 31, lane);
-  }
+  wgrad(std::integral_constant<int, 2>{}, dc0);
   f32x16 ds1 = gemm<R_B2G>(P, 0, zero16(), lane, [&](int s) { return dc0[s >> 4][s & 15]; });
-  if (h == 0) ds1[0] = dsig;                    // row 0 = sigma (A row 0 is zero)
+  if (h == 0) ds1[0] = dr.w;                    // row 0 = sigma (A row 0 is zero)
   if (dsh != nullptr)
     *dsh = gemm<R_B2S>(P, 0, zero16(), lane, [&](int s) { return dc0[s >> 4][s & 15]; });
-  // ---- sigma_net.1 ----
-  stage_tile(Tdy, ds1, lane);
-#pragma unroll
-  for (int kb = 0; kb < 2; ++kb) {
-    stage_tile(Tx, a.h0[kb], lane);
-    wgrad_accum(Tdy, Tx, Wacc, W_S1, 64, 0, 16, kb * 32, 64, lane);
-  }
-  f32x16 dh0[2];
+  wgrad(std::integral_constant<int, 1>{}, &ds1);
 #pragma unroll
   for (int ob = 0; ob < 2; ++ob) {
     dh0[ob] = gemm<R_B1>(P, ob, zero16(), lane, [&](int s) { return ds1[s]; });
-    mask16(dh0[ob], a.h0[ob]);
+    relu(dh0[ob], 0, ob);
   }
-  // ---- sigma_net.0 ----
-  stage_tile(Tx, feat, lane);
-#pragma unroll
-  for (int nb = 0; nb < 2; ++nb) {
-    stage_tile(Tdy, dh0[nb], lane);
-    wgrad_accum(Tdy, Tx, Wacc, W_S0, 32, nb * 32, 64, 0, 32, lane);
-  }
+  wgrad(std::integral_constant<int, 0>{}, dh0);
   dfeat = gemm<R_B0>(P, 0, zero16(), lane, [&](int s) { return dh0[s >> 4][s & 15]; });
 }
 

@@ -72,14 +72,69 @@ __global__ __launch_bounds__(256, 2) void mlp_bwd_kernel(const float* __restrict
     f32x16 c2;
     mlp_fwd_tile(Pt, feat, sh8, a, c2, lane);
     const float4 g = valid ? *reinterpret_cast<const float4*>(dout + 4 * q) : make_float4(0, 0, 0, 0);
-    const float dy2[2] = {h ? g.y : g.x, h ? 0.f : g.z};
-    const float rgbg[3] = {g.x, g.y, g.z};
-    float shx8[8];
+    float shx8[8];   // sh[8h .. 8h + 7] of the point
 #pragma unroll
     for (int j = 0; j < 8; ++j) shx8[j] = h ? sh_pt[8 + j] : sh_pt[j];
+    float* Tdy = T;
+    float* Tx = T + kTBuf;
     f32x16 dfeat, dsh;
-    mlp_bwd_tile(Pt, feat, shx8, a, dy2, g.w, rgbg, T, Wacc, dfeat,
-                 dx != nullptr ? &dsh : nullptr, lane);
+    mlp_bwd_tile(
+        Pt, g, [&](f32x16& v, int l, int ob) { mask16(v, l == 2 ? a.c1[ob] : l == 1 ? a.c0[ob] : a.h0[ob]); },
+        // each layer's dW: both operands staged through the wave's transpose buffers
+        [&](auto lc, const f32x16* dy) {
+          constexpr int l = decltype(lc)::value;
+          if constexpr (l == 4) {          // color_net.2: dY = the rgb grads
+            if (h == 0) {
+              Tdy[p * kTS + 0] = g.x;
+              Tdy[p * kTS + 1] = g.y;
+              Tdy[p * kTS + 2] = g.z;
+            }
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+              stage_tile(Tx, a.c1[kb], lane);
+              wgrad_accum(Tdy, Tx, Wacc, W_C2, 64, 0, 3, kb * 32, 64, lane);
+            }
+          } else if constexpr (l == 3) {   // color_net.1
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+              stage_tile(Tdy, dy[nb], lane);
+#pragma unroll
+              for (int kk = 0; kk < 2; ++kk) {
+                const int kb = nb ? 1 - kk : kk;   // reuse the staged X block across nb
+                if (!(nb == 1 && kk == 0)) stage_tile(Tx, a.c0[kb], lane);
+                wgrad_accum(Tdy, Tx, Wacc, W_C1, 64, nb * 32, 64, kb * 32, 64, lane);
+              }
+            }
+          } else if constexpr (l == 2) {   // color_net.0: X = [sh16 | geo15]
+#pragma unroll
+            for (int j = 0; j < 8; ++j) Tx[p * kTS + 8 * h + j] = shx8[j];
+#pragma unroll
+            for (int r = 0; r < 8; ++r) {
+              const int row = row_of(r, h);               // s1 rows 0..15
+              if (row >= 1) Tx[p * kTS + 15 + row] = a.s1[r];
+            }
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+              stage_tile(Tdy, dy[nb], lane);
+              wgrad_accum(Tdy, Tx, Wacc, W_C0, 31, nb * 32, 64, 0, 31, lane);
+            }
+          } else if constexpr (l == 1) {   // sigma_net.1
+            stage_tile(Tdy, dy[0], lane);
+#pragma unroll
+            for (int kb = 0; kb < 2; ++kb) {
+              stage_tile(Tx, a.h0[kb], lane);
+              wgrad_accum(Tdy, Tx, Wacc, W_S1, 64, 0, 16, kb * 32, 64, lane);
+            }
+          } else {               // sigma_net.0
+            stage_tile(Tx, feat, lane);
+#pragma unroll
+            for (int nb = 0; nb < 2; ++nb) {
+              stage_tile(Tdy, dy[nb], lane);
+              wgrad_accum(Tdy, Tx, Wacc, W_S0, 32, nb * 32, 64, 0, 32, lane);
+            }
+          }
+        },
+        dfeat, dx != nullptr ? &dsh : nullptr, lane);
     if (dx != nullptr && valid) {
       float* row = dx + q * 48;
 #pragma unroll

@@ -10,10 +10,11 @@
 // runs across GEMM and tile boundaries.  ReLU masks are kept as bits.  The
 // composite backward (d raw per sample) comes from a full-occupancy pre-pass
 // (render_comp_bwd_kernel).
-// b1_tile is the tile; which tiles a wave runs, and where their feature grads
-// go, is the schedule's (b1_groups in hn_bwd_binned.h, b1_unit in
-// hn_bwd_atomic.h).  After the kernel, dw_flush stores a wave's accumulators
-// to its dW slab and slab_reduce_block sums the slabs in a fixed order.
+// b1_tile is the tile and c0sh_setup its rays' set-up; which tiles a wave
+// runs, and where their feature grads go, is the schedule's (b1_groups in
+// hn_bwd_binned.h, b1_unit in hn_bwd_atomic.h).  After the kernel, dw_flush
+// stores a wave's accumulators to its dW slab and slab_reduce_block sums the
+// slabs in a fixed order.
 #pragma once
 #include "hn_render_args.h"
 
@@ -61,8 +62,8 @@ struct DW {
 // two split-f32 parts (hn_common.h: p0 = bf16(x), p1 = bf16(x - p0), the NS = 2
 // split of the dW products) in a per-wave image [32 points][32 features] of
 // bf16 per part (64-B point rows).  The parts come from the split the tile
-// already gets as the B operand of the next GEMM of the chain (gemm_w / _w2
-// with an image sink), so the dW products need no split of their own.
+// already gets as the B operand of the next GEMM of the chain (gemm_w with
+// an image sink), so the dW products need no split of their own.
 // dW[o][i] = sum_p G[o][p] X[i][p] contracts the point index (X's column),
 // so both operands are read back transposed by ds_read_b64_tr_b16: lane l
 // gets feature l & 31 of 4 consecutive points per read.  The 8-byte feature
@@ -152,7 +153,7 @@ HN_DEV void static_for(F&& f) {
 
 // A weight-gradient block's operands read into registers ahead of its
 // products (WgOps), and the products then issued in the gaps of a later
-// data-path GEMM (WgX, gemm_w / gemm_w2's `xt`): the image reads leave before
+// data-path GEMM (WgX, gemm_w's `xt`): the image reads leave before
 // that GEMM's own image writes (a wave's LDS accesses execute in order), and
 // the products -- the same ones, per accumulator in the same order as
 // wgrad_n's -- keep the matrix pipe busy while the chain waits on its own
@@ -206,7 +207,7 @@ struct WgX {
 // flight across GEMM, tile and unit boundaries: no GEMM starts on an exposed
 // L2 latency at one wave per SIMD.  Depth 4 measured 484 us for the config-2
 // MLP backward, 8: 460 us.  The two output blocks of a GEMM are paired
-// (kSegs, gemm_w2): one B split per chunk for both, two independent
+// (kSegs, gemm_w's NB = 2): one B split per chunk for both, two independent
 // accumulator chains (515 -> 484 us together with wgrad_n's shared splits).
 struct GemmSeg {
   int r, ob;   // region (hn_mlp.h), output block; ob = -1: both blocks, chunk by chunk
@@ -286,7 +287,7 @@ HN_DEV f32x4 wring_take(WRing& w, const float* P, int lane) {
 // 0.812 -> 0.789 ms, step 1.159 -> 1.134 ms; the kernel's 24 VGPR spills go to 0.
 // The same pipelining in the forward's gemm (round 3, removed) changed
 // nothing there (render_fwd 0.304 ms either way).
-// (VALU per MFMA slot, 2-part splits: 7 in gemm_w, 4 in gemm_w2.  Measured
+// (VALU per MFMA slot, 2-part splits: 7 for one block, 4 for a pair.  Measured
 // round 4, r04sw: 5 / 3 took render_bwd_kernel from 0.2343 to 0.2426 ms,
 // 10 / 6 to 0.2364 ms.)
 template <int NMFMA, int NVALU>
@@ -297,7 +298,9 @@ HN_DEV void swp_pattern() {
   });
 }
 
-// acc += A(segment SEG of the stream) . B, bval(s) = B operand of f32 k-step s.
+// acc[b] += A(block b of segment SEG of the stream) . B for the segment's NB
+// output blocks (2: a paired segment -- one B split per chunk for both blocks,
+// and two independent accumulator chains); bval(s) = B operand of f32 k-step s.
 // IMG >= 0: chunk c's first two B parts also go to image tile IMG + c / 2 at
 // quad offset F4B + 4 (c % 2) (put_parts; Xb = the wave's images).
 // XT: extra independent MFMAs issued after chunk c's own (WgX; NoX: none),
@@ -305,121 +308,61 @@ HN_DEV void swp_pattern() {
 template <int NS, bool PAIR>
 constexpr int kSplitV = NS == 3 ? 36 : (PAIR ? 24 : 21);
 constexpr int ceil_div(int a, int b) { return (a + b - 1) / b; }
-template <int SEG, int IMG = -1, int F4B = 0, typename BF, typename XT = NoX>
-HN_DEV f32x16 gemm_w(WRing& w, const float* P, f32x16 acc, int lane, BF bval, char* Xb = nullptr,
-                     const XT& xt = XT{}) {
+template <int SEG, int NB, int IMG = -1, int F4B = 0, typename BF, typename XT = NoX>
+HN_DEV void gemm_w(WRing& w, const float* P, f32x16* acc, int lane, BF bval, char* Xb = nullptr,
+                   const XT& xt = XT{}) {
   constexpr int R = kSegs[SEG].r, KS = kRegKS[R], NS = seg_ns(kSegs[SEG]), START = seg_start(SEG);
+  static_assert(NB == (kSegs[SEG].ob < 0 ? 2 : 1), "a paired segment yields both blocks, any other one");
   static_assert(IMG < 0 || NS >= 2, "image sinks take split B operands");
+  // chunk c's A parts off the ring: block 0's NS groups, then block 1's
+  auto take = [&](auto cc, SP<NS>(&a)[NB]) {
+    static_for<0, NB * NS>([&](auto ic) {
+      constexpr int c = decltype(cc)::value, i = decltype(ic)::value;
+      a[i / NS].p[i % NS] = as_bf16x8(wring_take<START + NB * NS * c + i>(w, P, lane));
+    });
+  };
   if constexpr (NS > 0 && KS > 8) {   // split-f32, next chunk's split in the MFMA gaps
     constexpr int NC = KS / 8;
     SP<NS> b = splitn<NS>([&](int j) { return bval(j); });
     __builtin_amdgcn_sched_barrier(0);
     static_for<0, NC>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
-      SP<NS> a;
-      static_for<0, NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        a.p[q] = as_bf16x8(wring_take<START + NS * c + q>(w, P, lane));
-      });
+      SP<NS> a[NB];
+      take(cc, a);
       if constexpr (IMG >= 0) put_parts<NS>(Xb, IMG + c / 2, F4B + 4 * (c % 2), b, lane);
-      acc = mfma_split<NS>(a, b, acc);
+      mfma_split<NS, NB>(a, b, acc);
       xt.template run<c>();
       if constexpr (c + 1 < NC) {
         b = splitn<NS>([&](int j) { return bval(8 * (c + 1) + j); });
-        constexpr int M = NS + XT::per(c);
-        swp_pattern<M, XT::per(c) ? ceil_div(kSplitV<NS, false>, M) : (NS == 3 ? 6 : 7)>();
+        constexpr int M = NB * NS + XT::per(c);
+        constexpr int V = NB == 2 ? (NS == 3 ? 3 : 4) : (NS == 3 ? 6 : 7);   // VALU per MFMA slot (above)
+        swp_pattern<M, XT::per(c) ? ceil_div(kSplitV<NS, NB == 2>, M) : V>();
       }
       __builtin_amdgcn_sched_barrier(0);
     });
-  } else if constexpr (NS > 0) {                // split-f32: NS groups per K = 16 chunk
+  } else if constexpr (NS > 0) {                // split-f32: NS groups per block and K = 16 chunk
     static_for<0, KS / 8>([&](auto cc) {
       constexpr int c = decltype(cc)::value;
-      SP<NS> a;
-      static_for<0, NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        a.p[q] = as_bf16x8(wring_take<START + NS * c + q>(w, P, lane));
-      });
+      SP<NS> a[NB];
+      take(cc, a);
       const SP<NS> b = splitn<NS>([&](int j) { return bval(8 * c + j); });
       if constexpr (IMG >= 0) put_parts<NS>(Xb, IMG + c / 2, F4B + 4 * (c % 2), b, lane);
-      acc = mfma_split<NS>(a, b, acc);
+      mfma_split<NS, NB>(a, b, acc);
       xt.template run<c>();
       __builtin_amdgcn_sched_barrier(0);
     });
   } else {
     static_for<0, KS / 4>([&](auto gc) {
       constexpr int g = decltype(gc)::value;
-      const f32x4 a = wring_take<START + g>(w, P, lane);
+      f32x4 a[NB];
+      static_for<0, NB>([&](auto bc) {
+        constexpr int b = decltype(bc)::value;
+        a[b] = wring_take<START + NB * g + b>(w, P, lane);
+      });
 #pragma unroll
-      for (int j = 0; j < 4; ++j) acc = mfma(a[j], bval(4 * g + j), acc);
-      xt.template run<g>();
-      __builtin_amdgcn_sched_barrier(0);
-    });
-  }
-  return acc;
-}
-
-// acc0 / acc1 += blocks 0 / 1 of the paired segment SEG . B: one B split per
-// chunk for both blocks, and two independent accumulator chains
-template <int SEG, int IMG = -1, int F4B = 0, typename BF, typename XT = NoX>
-HN_DEV void gemm_w2(WRing& w, const float* P, f32x16& acc0, f32x16& acc1, int lane, BF bval, char* Xb = nullptr,
-                    const XT& xt = XT{}) {
-  constexpr int R = kSegs[SEG].r, KS = kRegKS[R], NS = seg_ns(kSegs[SEG]), START = seg_start(SEG);
-  static_assert(kSegs[SEG].ob < 0, "paired segment");
-  static_assert(IMG < 0 || NS >= 2, "image sinks take split B operands");
-  if constexpr (NS > 0 && KS > 8) {
-    constexpr int NC = KS / 8;
-    SP<NS> b = splitn<NS>([&](int j) { return bval(j); });
-    __builtin_amdgcn_sched_barrier(0);
-    static_for<0, NC>([&](auto cc) {
-      constexpr int c = decltype(cc)::value;
-      SP<NS> a0, a1;
-      static_for<0, NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        a0.p[q] = as_bf16x8(wring_take<START + 2 * NS * c + q>(w, P, lane));
-      });
-      static_for<0, NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        a1.p[q] = as_bf16x8(wring_take<START + 2 * NS * c + NS + q>(w, P, lane));
-      });
-      if constexpr (IMG >= 0) put_parts<NS>(Xb, IMG + c / 2, F4B + 4 * (c % 2), b, lane);
-      mfma_split2<NS>(a0, a1, b, acc0, acc1);
-      xt.template run<c>();
-      if constexpr (c + 1 < NC) {
-        b = splitn<NS>([&](int j) { return bval(8 * (c + 1) + j); });
-        constexpr int M = 2 * NS + XT::per(c);
-        swp_pattern<M, XT::per(c) ? ceil_div(kSplitV<NS, true>, M) : (NS == 3 ? 3 : 4)>();
-      }
-      __builtin_amdgcn_sched_barrier(0);
-    });
-  } else if constexpr (NS > 0) {
-    constexpr int NC = KS / 8;
-    static_for<0, NC>([&](auto cc) {
-      constexpr int c = decltype(cc)::value;
-      SP<NS> a0, a1;
-      static_for<0, NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        a0.p[q] = as_bf16x8(wring_take<START + 2 * NS * c + q>(w, P, lane));
-      });
-      static_for<0, NS>([&](auto qc) {
-        constexpr int q = decltype(qc)::value;
-        a1.p[q] = as_bf16x8(wring_take<START + 2 * NS * c + NS + q>(w, P, lane));
-      });
-      const SP<NS> b = splitn<NS>([&](int j) { return bval(8 * c + j); });
-      if constexpr (IMG >= 0) put_parts<NS>(Xb, IMG + c / 2, F4B + 4 * (c % 2), b, lane);
-      mfma_split2<NS>(a0, a1, b, acc0, acc1);
-      xt.template run<c>();
-      __builtin_amdgcn_sched_barrier(0);
-    });
-  } else {
-    static_for<0, KS / 4>([&](auto gc) {
-      constexpr int g = decltype(gc)::value;
-      const f32x4 a0 = wring_take<START + 2 * g>(w, P, lane);
-      const f32x4 a1 = wring_take<START + 2 * g + 1>(w, P, lane);
+      for (int j = 0; j < 4; ++j)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        acc0 = mfma(a0[j], bval(4 * g + j), acc0);
-        acc1 = mfma(a1[j], bval(4 * g + j), acc1);
-      }
+        for (int b = 0; b < NB; ++b) acc[b] = mfma(a[b][j], bval(4 * g + j), acc[b]);
       xt.template run<g>();
       __builtin_amdgcn_sched_barrier(0);
     });
@@ -431,17 +374,18 @@ constexpr int seg_of(int r) {   // first stream segment of region r
     if (kSegs[i].r == r) return i;
   return -1;
 }
-// acc[0..1] += both output blocks of region R . B (image sink: gemm_w)
+// acc[0..1] += both output blocks of region R . B: one paired segment, or
+// a segment per block (the image sink on the first)
 template <int R, int IMG = -1, int F4B = 0, typename BF, typename XT = NoX>
 HN_DEV void gemm2(WRing& w, const float* P, f32x16 acc[2], int lane, BF bval, char* Xb = nullptr,
                   const XT& xt = XT{}) {
   constexpr int S = seg_of(R);
   if constexpr (kSegs[S].ob < 0) {
-    gemm_w2<S, IMG, F4B>(w, P, acc[0], acc[1], lane, bval, Xb, xt);
+    gemm_w<S, 2, IMG, F4B>(w, P, acc, lane, bval, Xb, xt);
   } else {
     static_assert(std::is_same<XT, NoX>::value, "extra products go to paired segments");
-    acc[0] = gemm_w<S, IMG, F4B>(w, P, acc[0], lane, bval, Xb);
-    acc[1] = gemm_w<S + 1>(w, P, acc[1], lane, bval);
+    gemm_w<S, 1, IMG, F4B>(w, P, acc, lane, bval, Xb);
+    gemm_w<S + 1, 1>(w, P, acc + 1, lane, bval);
   }
 }
 
@@ -500,6 +444,44 @@ HN_DEV void c0sh_seed(const C0Sh& c, f32x16 (&c0)[2], int h) {
     }
 }
 
+// The set-up of a tile's rays ahead of b1_tile.  The SH part of color_net.0's
+// input (each lane's ray gives its point's columns: features 8h .. 8h + 7 of
+// the [sh16 | sigma | geo15] image) goes to the kBC0in image; color_net.0 is
+// applied to the SH features (column p of that product is point p's ray; bit-
+// identical to starting each point's chain with it) and its 64 rows are kept
+// at X + kC0shF.  kGroups false: one ray for the 32 points, column 0 (lanes 0
+// and 32 store).  true: points 0-15 and 16-31 are of two rays, columns 0 and
+// 16, 64 floats apart; a lane's C0Sh is its own group's.
+template <bool kGroups>
+HN_DEV C0Sh c0sh_setup(const float* P, const Ray& r, float* X, int lane) {
+  const int p = lane & 31, h = lane >> 5;
+  float sh8[8], shx8[8];
+  ray_sh(r, h, sh8, shx8);
+  const SP<2> sp = splitn<2>([&](int j) { return shx8[j]; });
+  // point p's 64-B row first, then the swizzled quad in it (img_off's sum in this order)
+  char* Xp = reinterpret_cast<char*>(X) + 64 * p;
+  const int sw = (p >> 1) & 7;
+#pragma unroll
+  for (int q = 0; q < 2; ++q) {
+    const u32x4 w = __builtin_bit_cast(u32x4, sp.p[q]);
+    put_quad(Xp, kBC0in, q, 0, (2 * h) ^ sw, w[0], w[1]);
+    put_quad(Xp, kBC0in, q, 0, (2 * h + 1) ^ sw, w[2], w[3]);
+  }
+  float* cl = X + kC0shF;
+  const int grp = kGroups ? 64 * (p >> 4) : 0;   // the lane's group's rows
+#pragma unroll
+  for (int ob = 0; ob < 2; ++ob) {
+    const f32x16 v = gemm<R_F2S>(P, ob, zero16(), lane, [&](int s) { return sh8[s]; });
+    if ((kGroups ? p & 15 : p) == 0)
+#pragma unroll
+      for (int g = 0; g < 4; ++g)
+        *reinterpret_cast<f32x4*>(cl + grp + 32 * ob + row_of(4 * g, h)) =
+            f32x4{v[4 * g], v[4 * g + 1], v[4 * g + 2], v[4 * g + 3]};
+  }
+  lds_fence_wave();
+  return C0Sh{cl + grp};
+}
+
 // One 32-point tile: recompute the forward (features from the cache), then
 // the MLP backward; dW into the wave's accumulators, d feature to dst.
 HN_DEV f32x16 b1_tile(const float* __restrict__ P, WRing& wr, float* X, const f32x16& feat,
@@ -515,7 +497,8 @@ HN_DEV f32x16 b1_tile(const float* __restrict__ P, WRing& wr, float* X, const f3
   gemm2<R_F0, kBF>(wr, P, h0, lane, [&](int s) { return feat[s]; }, Xb);
   HN_RELU(h0[0], mh0, 0);
   HN_RELU(h0[1], mh0, 1);
-  const f32x16 s1 = gemm_w<seg_of(R_F1), kBH0>(wr, P, zero16(), lane, [&](int s) { return h0[s >> 4][s & 15]; }, Xb);
+  f32x16 s1 = zero16();
+  gemm_w<seg_of(R_F1), 1, kBH0>(wr, P, &s1, lane, [&](int s) { return h0[s >> 4][s & 15]; }, Xb);
   f32x16 c0[2];
   c0sh_seed(c0sh, c0, h);
   // s1 rows 0..15 = [sigma | geo15] -> features 16..31 of [sh16 | sigma | geo15]
@@ -567,8 +550,9 @@ HN_DEV f32x16 b1_tile(const float* __restrict__ P, WRing& wr, float* X, const f3
     const int ab[2] = {kBC1, kBC1 + 1}, bb[2] = {kBC0, kBC0 + 1};
     wg_load(w_c1, Xb, ab, bb, lane);            // dw.c1[2 * nb + kb]
   }
-  f32x16 ds1 = gemm_w<seg_of(R_B2G), kBC0>(wr, P, zero16(), lane, [&](int s) { return dc0[s >> 4][s & 15]; }, Xb,
-                                           WgX<2, 2, 4>{w_c1, dw.c1});
+  f32x16 ds1 = zero16();
+  gemm_w<seg_of(R_B2G), 1, kBC0>(wr, P, &ds1, lane, [&](int s) { return dc0[s >> 4][s & 15]; }, Xb,
+                                 WgX<2, 2, 4>{w_c1, dw.c1});
   if (h == 0) ds1[0] = dr.w;                    // row 0 = sigma (A row 0 is zero)
   tile_lds_order();
   // ---- sigma_net.1 (ds1 image over dc1's first tile; rows 16..31 discarded), color_net.0's dW inside ----
@@ -588,8 +572,9 @@ HN_DEV f32x16 b1_tile(const float* __restrict__ P, WRing& wr, float* X, const f3
     const int ab[1] = {kBC1}, bb[2] = {kBH0, kBH0 + 1};
     wg_load(w_s1, Xb, ab, bb, lane);
   }
-  const f32x16 dfeat = gemm_w<seg_of(R_B0), kBC0>(wr, P, zero16(), lane, [&](int s) { return dh0[s >> 4][s & 15]; },
-                                                  Xb, WgX<1, 2, 4>{w_s1, dw.s1});
+  f32x16 dfeat = zero16();
+  gemm_w<seg_of(R_B0), 1, kBC0>(wr, P, &dfeat, lane, [&](int s) { return dh0[s >> 4][s & 15]; }, Xb,
+                                WgX<1, 2, 4>{w_s1, dw.s1});
   tile_lds_order();
   {
     const int ab[2] = {kBC0, kBC0 + 1}, bb[1] = {kBF};

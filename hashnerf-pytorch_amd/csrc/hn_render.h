@@ -1,7 +1,9 @@
 // hn_render.h -- per-ray (one wave64 per ray) volume rendering building blocks:
-//   composite_fwd / composite_bwd  raw2outputs (run_nerf_helpers.py:577-628)
+//   composite_fwd / composite_bwd  raw2outputs (run_nerf_helpers.py:577-628);
+//                                  composite_dalpha: the d alpha both of its
+//                                  backwards (d raw; d z and d |d|) start from
 //   sample_pdf_wave                sample_pdf  (run_nerf_helpers.py:264-307)
-//   rank_sort_wave                 torch.sort of the merged z  (:551)
+//   rank_sort_wave, merge_sort_z   torch.sort of the merged z  (:551)
 //
 // Samples of a ray are "blocked" over lanes: lane l owns samples l*N .. l*N+N-1
 // (N = ceil(S/64), template parameter).  Per-ray arrays live in LDS (or global)
@@ -174,13 +176,13 @@ struct CompGrad {
   bool has_rgb, has_acc, has_depth, has_entropy;
 };
 
-// Backward w.r.t. raw from a ray's samples and totals (composite_bwd's second
-// half): writes draw[j] (float4; may alias the raw the samples were read
-// from).  gw: per-sample grad of weights or null; graw: external grad of raw
-// (added) or null.
+// d loss / d alpha_k of a ray's samples: G_k, the
+// upstream gradient of weight k; the suffix sums of G w over later samples;
+// dalpha_k = G_k T_k - Sfx_k / x_k.  gw: per-sample grad of weights or null.
+// dalpha[k] of a sample that is not valid is unspecified and must not be read.
 template <int N>
-HN_DEV void composite_bwd_raw(const CompSamples<N>& cs, const CompTotals& t, bool white, const CompGrad& g,
-                              const float* gw, const float* graw, float* draw, int lane) {
+HN_DEV void composite_dalpha(const CompSamples<N>& cs, const CompTotals& t, bool white, const CompGrad& g,
+                             const float* gw, float (&dalpha)[N], int lane) {
   // entropy: dH/dw_j = (g_j - g_S) / Q with g_k = -(log(clamp p_k) + inside_k)
   const float pS = t.qS / t.Q;
   const float gS = -(ent_logit(pS) + (ent_inside(pS) ? 1.f : 0.f));
@@ -208,11 +210,23 @@ HN_DEV void composite_bwd_raw(const CompSamples<N>& cs, const CompTotals& t, boo
   }
   excl_suffix_sum<N>(Gw, Sfx, lane);
 #pragma unroll
+  for (int k = 0; k < N; ++k) dalpha[k] = G[k] * cs.T[k] - (float)Sfx[k] / cs.x[k];
+}
+
+// Backward w.r.t. raw from a ray's samples and totals (composite_bwd's second
+// half): writes draw[j] (float4; may alias the raw the samples were read
+// from).  gw: per-sample grad of weights or null; graw: external grad of raw
+// (added) or null.
+template <int N>
+HN_DEV void composite_bwd_raw(const CompSamples<N>& cs, const CompTotals& t, bool white, const CompGrad& g,
+                              const float* gw, const float* graw, float* draw, int lane) {
+  float dalpha[N];
+  composite_dalpha<N>(cs, t, white, g, gw, dalpha, lane);
+#pragma unroll
   for (int k = 0; k < N; ++k) {
     const int j = lane * N + k;
     if (!cs.valid[k]) continue;
-    const float dalpha = G[k] * cs.T[k] - (float)Sfx[k] / cs.x[k];
-    const float dsig_t = dalpha * cs.e[k] * cs.delta[k];
+    const float dsig_t = dalpha[k] * cs.e[k] * cs.delta[k];
     float4 d;
     d.w = cs.sig[k] > 0.f ? dsig_t : 0.f;
     if (g.has_rgb) {
@@ -243,9 +257,8 @@ HN_DEV void composite_bwd(const float* raw, const float* z, const float* noise, 
   composite_bwd_raw<N>(cs, t, white, g, gw, graw, draw, lane);
 }
 
-// Backward w.r.t. z and |d| of one ray.  d loss / d alpha_k is formed exactly
-// as composite_bwd_raw forms it (the same G, suffix sums and dalpha); from
-// there d delta_k = dalpha_k * e_k * sig_k (alpha = 1 - exp(-sig * delta)),
+// Backward w.r.t. z and |d| of one ray.  From composite_dalpha's d loss /
+// d alpha_k, d delta_k = dalpha_k * e_k * sig_k (alpha = 1 - exp(-sig * delta)),
 // delta_k = (z[k+1] - z[k]) * |d|, the last one 1e10 * |d| (:590-593):
 //   d z_j = (d delta_{j-1} - d delta_j) * |d| + w_j * g_depth / acc
 //   d |d| = sum_k d delta_k * dist_k
@@ -254,39 +267,16 @@ template <int N>
 HN_DEV float composite_bwd_inputs(const CompSamples<N>& cs, const CompTotals& t, const float* z, int S,
                                   float dnorm, bool white, const CompGrad& g, const float* gw, float* dz,
                                   int lane) {
-  const float pS = t.qS / t.Q;
-  const float gS = -(ent_logit(pS) + (ent_inside(pS) ? 1.f : 0.f));
-  const float white_term = (g.has_rgb && white) ? -(g.rgb[0] + g.rgb[1] + g.rgb[2]) : 0.f;
+  float dalpha[N];
+  composite_dalpha<N>(cs, t, white, g, gw, dalpha, lane);
   const float gd_over_a = g.has_depth ? g.depth / t.acc : 0.f;
-  const float gd_num = g.has_depth ? -(g.depth * t.num) / (t.acc * t.acc) : 0.f;
-  float G[N];
-  double Gw[N], Sfx[N];
-#pragma unroll
-  for (int k = 0; k < N; ++k) {
-    float gk = 0.f;
-    if (cs.valid[k]) {
-      if (g.has_rgb) gk = g.rgb[0] * cs.c[k][0] + g.rgb[1] * cs.c[k][1] + g.rgb[2] * cs.c[k][2] + white_term;
-      if (g.has_acc) gk += g.acc;
-      if (g.has_depth) gk += cs.z[k] * gd_over_a + gd_num;
-      if (g.has_entropy) {
-        const float p = cs.w[k] / t.Q;
-        const float gp = -(ent_logit(p) + (ent_inside(p) ? 1.f : 0.f));
-        gk += g.entropy * ((gp - gS) / t.Q);
-      }
-      if (gw != nullptr) gk += gw[lane * N + k];
-    }
-    G[k] = gk;
-    Gw[k] = (double)(gk * cs.w[k]);
-  }
-  excl_suffix_sum<N>(Gw, Sfx, lane);
   float dd[N];          // d loss / d dist_k
   double dn = 0.0;
 #pragma unroll
   for (int k = 0; k < N; ++k) {
     dd[k] = 0.f;
     if (!cs.valid[k]) continue;
-    const float dalpha = G[k] * cs.T[k] - (float)Sfx[k] / cs.x[k];
-    const float ddelta = dalpha * cs.e[k] * cs.sig[k];
+    const float ddelta = dalpha[k] * cs.e[k] * cs.sig[k];
     const int j = lane * N + k;
     const float dist = (j + 1 < S) ? z[j + 1] - cs.z[k] : 1e10f;   // composite_samples' dist
     dn += (double)(ddelta * dist);
@@ -432,47 +422,54 @@ HN_DEV uint32_t sort_key(float v) {
 }
 HN_DEV float key_value(uint32_t k) { return __uint_as_float(k ^ ((k >> 31) ? 0x80000000u : 0xffffffffu)); }
 
-// The same result as rank_sort_wave(src, dst, 192, lane, origin, 64) -- the
-// values torch.sort returns, and origin[rank] = the coarse index or 255 --
-// for src = [64 coarse z, non-decreasing | 128 importance z]: the importance
-// samples are sorted by a bitonic network over the wave (2 per lane, cross-
-// lane exchanges by ds_bpermute), then each element's rank is its position in
-// its own run plus a binary search in the other run (coarse before importance
-// on ties, as the rank sort's index tie-break puts them; ties among importance
-// samples are equal values tagged 255, so their order is not observable).
-// ~0.5 k instructions per wave where the rank sort's 192 x 192 compares take
-// ~3 k.  Returns false (dst untouched) when the coarse run is not sorted.
+// The same result as rank_sort_wave(src, dst, 64 + 64 * NI, lane, origin, 64)
+// -- the values torch.sort returns, and origin[rank] = the coarse index or 255
+// -- for src = [64 coarse z, non-decreasing | 64 * NI importance z], NI
+// importance samples per lane (2 for 128 + 64, 1 for 64 + 64): the importance
+// samples are sorted by a bitonic network over the wave (cross-lane exchanges
+// by ds_bpermute; NI = 1 never leaves the lane's one register: 6 stages, 21
+// exchanges), then each element's rank is its position in its own run plus a
+// binary search in the other run (coarse before importance on ties, as the
+// rank sort's index tie-break puts them; ties among importance samples are
+// equal values tagged 255, so their order is not observable).  ~0.5 k
+// instructions per wave where the rank sort's 192 x 192 compares take ~3 k.
+// tmp: 64 * NI floats.  Returns false (dst untouched) when the coarse run is
+// not sorted.
+template <int NI>
 HN_DEV bool merge_sort_z(const float* src, float* dst, float* tmp, int lane, uint8_t* origin) {
+  static_assert(NI == 1 || NI == 2, "one or two importance samples per lane");
   const float zc = src[lane];
   const float zn = lane < 63 ? src[lane + 1] : zc;
   if (__ballot(sort_key(zn) < sort_key(zc)) != 0ull) return false;
-  uint32_t k[2] = {sort_key(src[64 + lane]), sort_key(src[128 + lane])};
+  uint32_t k[NI];
 #pragma unroll
-  for (int kk = 2; kk <= 128; kk <<= 1) {
+  for (int r = 0; r < NI; ++r) k[r] = sort_key(src[64 + 64 * r + lane]);
+#pragma unroll
+  for (int kk = 2; kk <= 64 * NI; kk <<= 1) {
 #pragma unroll
     for (int j = kk >> 1; j > 0; j >>= 1) {
-      if (j == 64) {   // partner in the other register of this lane (kk = 128: ascending)
-        const uint32_t lo = min(k[0], k[1]), hi = max(k[0], k[1]);
+      if (j == 64) {   // NI == 2: partner in the other register of this lane (kk = 128: ascending)
+        const uint32_t lo = min(k[0], k[NI - 1]), hi = max(k[0], k[NI - 1]);
         k[0] = lo;
-        k[1] = hi;
+        k[NI - 1] = hi;
       } else {
 #pragma unroll
-        for (int r = 0; r < 2; ++r) {
+        for (int r = 0; r < NI; ++r) {
           const int i = lane + 64 * r;
           const uint32_t kp = shfl_from(k[r], lane ^ j);
-          const bool asc = (i & kk) == 0, lower = (i & j) == 0;
+          const bool asc = (i & kk) == 0, lower = (i & j) == 0;   // the last kk: ascending over the run
           k[r] = (lower == asc) ? min(k[r], kp) : max(k[r], kp);
         }
       }
     }
   }
-  tmp[lane] = key_value(k[0]);
-  tmp[64 + lane] = key_value(k[1]);
+#pragma unroll
+  for (int r = 0; r < NI; ++r) tmp[64 * r + lane] = key_value(k[r]);
   lds_fence_wave();
   // coarse e: e + #{importance < v} (lower bound in the sorted importance run)
   {
     const uint32_t kc = sort_key(zc);
-    int lo = 0, hi = 128;
+    int lo = 0, hi = 64 * NI;
     while (lo < hi) {
       const int mid = (lo + hi) >> 1;
       if (sort_key(tmp[mid]) < kc) lo = mid + 1; else hi = mid;
@@ -482,7 +479,7 @@ HN_DEV bool merge_sort_z(const float* src, float* dst, float* tmp, int lane, uin
   }
   // importance at sorted position p: p + #{coarse <= v} (upper bound in the coarse run)
 #pragma unroll
-  for (int r = 0; r < 2; ++r) {
+  for (int r = 0; r < NI; ++r) {
     const int p = lane + 64 * r;
     int lo = 0, hi = 64;
     while (lo < hi) {
@@ -491,52 +488,6 @@ HN_DEV bool merge_sort_z(const float* src, float* dst, float* tmp, int lane, uin
     }
     dst[p + lo] = key_value(k[r]);
     if (origin) origin[p + lo] = (uint8_t)255;
-  }
-  lds_fence_wave();
-  return true;
-}
-
-// merge_sort_z for src = [64 coarse z, non-decreasing | 64 importance z]: the
-// same result as rank_sort_wave(src, dst, 128, lane, origin, 64).  One
-// importance sample per lane, so the bitonic network (6 stages, 21 exchanges)
-// never leaves the wave's one register; then the same two binary searches
-// (coarse before importance on ties).  tmp: 64 floats.
-HN_DEV bool merge_sort_z64(const float* src, float* dst, float* tmp, int lane, uint8_t* origin) {
-  const float zc = src[lane];
-  const float zn = lane < 63 ? src[lane + 1] : zc;
-  if (__ballot(sort_key(zn) < sort_key(zc)) != 0ull) return false;
-  uint32_t k = sort_key(src[64 + lane]);
-#pragma unroll
-  for (int kk = 2; kk <= 64; kk <<= 1) {
-#pragma unroll
-    for (int j = kk >> 1; j > 0; j >>= 1) {
-      const uint32_t kp = shfl_from(k, lane ^ j);
-      const bool asc = (lane & kk) == 0, lower = (lane & j) == 0;   // kk = 64: ascending over the wave
-      k = (lower == asc) ? min(k, kp) : max(k, kp);
-    }
-  }
-  tmp[lane] = key_value(k);
-  lds_fence_wave();
-  // coarse e: e + #{importance < v} (lower bound in the sorted importance run)
-  {
-    const uint32_t kc = sort_key(zc);
-    int lo = 0, hi = 64;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sort_key(tmp[mid]) < kc) lo = mid + 1; else hi = mid;
-    }
-    dst[lane + lo] = zc;
-    if (origin) origin[lane + lo] = (uint8_t)lane;
-  }
-  // importance at sorted position lane: lane + #{coarse <= v} (upper bound in the coarse run)
-  {
-    int lo = 0, hi = 64;
-    while (lo < hi) {
-      const int mid = (lo + hi) >> 1;
-      if (sort_key(src[mid]) <= k) lo = mid + 1; else hi = mid;
-    }
-    dst[lane + lo] = key_value(k);
-    if (origin) origin[lane + lo] = (uint8_t)255;
   }
   lds_fence_wave();
   return true;

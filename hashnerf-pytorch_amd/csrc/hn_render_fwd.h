@@ -204,7 +204,7 @@ HN_DEV void load_twin_feat(const float* tiles, int src, int h, f32x16& feat) {
 // (rawb is free until the fine tiles), the all-pairs rank sort if the coarse
 // run is ever out of order (render_fwd_kernel 0.2998 -> 0.2966 ms, r04c).
 // zsrc keeps the samples as drawn; org[i]: sorted sample i's coarse origin.
-// kNiT: the importance samples, kNi or kNi64 (its own one-register merge).
+// kNiT: the importance samples, kNi or kNi64 (merge_sort_z's NI = 2 or 1 per lane).
 template <int kNiT = kNi>
 HN_DEV void importance_sort(float* L, const float* u, uint8_t* org, int lane) {
   static_assert(kNiT == kNi || kNiT == kNi64, "importance_sort: 128 or 64 importance samples");
@@ -212,12 +212,8 @@ HN_DEV void importance_sort(float* L, const float* u, uint8_t* org, int lane) {
   lds_fence_wave();
   sample_pdf_wave(L + kFBins, L + kFW + 1, kSc - 2, L + kFCdf, u, kNiT, zsrc + kSc, lane);
   lds_fence_wave();
-  if constexpr (kNiT == kNi) {
-    if (!merge_sort_z(zsrc, L + kFZs, L + kFRaw, lane, org)) rank_sort_wave(zsrc, L + kFZs, kSf, lane, org, kSc);
-  } else {
-    if (!merge_sort_z64(zsrc, L + kFZs, L + kFRaw, lane, org))
-      rank_sort_wave(zsrc, L + kFZs, kSc + kNiT, lane, org, kSc);
-  }
+  if (!merge_sort_z<kNiT / 64>(zsrc, L + kFZs, L + kFRaw, lane, org))
+    rank_sort_wave(zsrc, L + kFZs, kSc + kNiT, lane, org, kSc);
 }
 
 // A pass's tiles: kPass 0 the coarse network (:540), 2 tiles at zc; 1 the fine

@@ -64,7 +64,7 @@ def test_render_takes_the_fused_path_at_64(hn):
 # ---- 2. the 64-sample merge ------------------------------------------------------
 @pytest.mark.parametrize("det", [False, True], ids=["perturb", "det"])
 def test_fine_z_sort_structure_64(hn, det):
-    """test_fine_z_sort_structure's assertions for merge_sort_z64 (B = 259):
+    """test_fine_z_sort_structure's assertions for merge_sort_z<1> (B = 259):
     fine z non-decreasing, each coarse index once in fine_src at its own value,
     the 64 others tagged 255, coarse first on ties (det: u = linspace(0, 1, 64)
     gives many exact ties)."""

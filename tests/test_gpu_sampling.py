@@ -1,6 +1,6 @@
 """Where the fused forward places each ray's samples, with no share of them
 left out: the coarse z (coarse_z, hn_render_fwd.h), sample_pdf_wave and the
-merge of the two runs (importance_sort: merge_sort_z / merge_sort_z64 and the
+merge of the two runs (importance_sort: merge_sort_z<2> / merge_sort_z<1> and the
 rank_sort_wave fallback), and the stand-alone hn_sample_pdf at its edges.
 
 The other oracle tests allow 3 % of the fine z to be anything, because samples
