@@ -153,6 +153,13 @@ class HnRayPool(C.Structure):
 
 
 POOL_ORDER_MAX = 8192           # HN_POOL_ORDER_MAX
+DENSITY_MAX_POINTS = 1 << 36    # HN_DENSITY_MAX_POINTS
+
+
+class HnLattice(C.Structure):
+    """hn_lattice: point (ix, iy, iz) sits at lo + (ix, iy, iz) * step; dims = (nx, ny, nz)."""
+    _fields_ = [("lo", C.c_float * 3), ("step", C.c_float * 3), ("dims", C.c_int32 * 3), ("reserved", C.c_int32)]
+
 
 # name -> (restype, argtypes); must match include/hashnerf_amd.h exactly.
 SIGNATURES = {
@@ -231,6 +238,10 @@ SIGNATURES = {
     "hn_render_bins": (C.c_int32, [C.POINTER(HnRenderCfg), C.c_int64, C.POINTER(C.c_int32)]),
     "hn_render_bwd_owner": (C.c_int32, [C.POINTER(HnRenderCfg), C.POINTER(HnRenderBwdArgs), _P,
                                         C.c_size_t, C.c_int32, C.c_int32, _P]),
+    "hn_density_points": (C.c_int32, [C.POINTER(HnGrid), C.POINTER(HnMlp), _P, _P, C.c_int64, C.c_float, _P, _P, _P,
+                                      C.c_size_t, _P]),
+    "hn_density_lattice": (C.c_int32, [C.POINTER(HnGrid), C.POINTER(HnMlp), _P, C.POINTER(HnLattice), C.c_float, _P,
+                                       _P, _P, C.c_size_t, _P]),
 }
 
 

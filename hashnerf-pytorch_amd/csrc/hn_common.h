@@ -39,6 +39,16 @@ inline GridArgs make_grid_args(const hn_grid& g) {
   return a;
 }
 
+// What every entry point taking an hn_grid accepts (hn_encode.hip's, the
+// density queries'): 1..HN_MAX_LEVELS levels of 2 features, T in 1..24.
+inline int32_t check_grid(const hn_grid* g) {
+  if (!g) return HN_E_NULL;
+  if (g->n_levels < 1 || g->n_levels > HN_MAX_LEVELS) return HN_E_SHAPE;
+  if (g->n_features != 2) return HN_E_SHAPE;
+  if (g->log2_hashmap_size < 1 || g->log2_hashmap_size > 24) return HN_E_SHAPE;
+  return HN_OK;
+}
+
 // torch.clamp(x, min=lo, max=hi) with NaN propagation (hash_encoding.py:69).
 HN_DEV float clamp_t(float x, float lo, float hi) {
   return x < lo ? lo : (x > hi ? hi : x);

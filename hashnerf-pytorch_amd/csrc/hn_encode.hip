@@ -159,14 +159,6 @@ __global__ __launch_bounds__(256) void sh_fwd_kernel(const float* __restrict__ d
   for (int i = 0; i < 4; ++i) dst[i] = make_float4(o[4 * i], o[4 * i + 1], o[4 * i + 2], o[4 * i + 3]);
 }
 
-static int32_t check_grid(const hn_grid* g) {
-  if (!g) return HN_E_NULL;
-  if (g->n_levels < 1 || g->n_levels > HN_MAX_LEVELS) return HN_E_SHAPE;
-  if (g->n_features != 2) return HN_E_SHAPE;
-  if (g->log2_hashmap_size < 1 || g->log2_hashmap_size > 24) return HN_E_SHAPE;
-  return HN_OK;
-}
-
 }  // namespace hn
 
 using namespace hn;

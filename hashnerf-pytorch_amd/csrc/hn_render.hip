@@ -3,7 +3,8 @@
 // pre-pass kernel of both backward schedules (not launched by the binned one
 // after a training forward that did its work, hn_render_fwd_args.loss), and
 // the host side; and hn_render_views / hn_render_image, the evaluation renderer
-// (whole images from poses, hn_render_image.h).  One
+// (whole images from poses, hn_render_image.h); and hn_density_points /
+// hn_density_lattice, the density queries (hn_density.h).  One
 // translation unit; the device code is in the headers (each says what it holds).
 #include "hn_render_args.h"   // kernel arguments, rays, feature cache, shared helpers
 #include "hn_render_fwd.h"    // render_fwd_kernel
@@ -12,9 +13,11 @@
 #include "hn_bwd_binned.h"    // binned schedule: render_bwd_kernel<kSwVmcnt, kModeSplit>, records, owner pass
 #include "hn_bwd_atomic.h"    // float-atomic fused schedule: render_bwd_kernel<CAP, kModeAtomic>
 #include "hn_bwd_rays.h"      // the ray gradient: render_bwd_rays_kernel and its reduction
+#include "hn_density.h"       // density queries: density_kernel (sigma / occupancy at points or on a lattice)
 
 #include <math.h>
 
+#include <algorithm>
 #include <atomic>
 #include <type_traits>
 
@@ -1054,4 +1057,72 @@ extern "C" int32_t hn_render_bwd_rays(const hn_render_cfg* cfg, const hn_render_
   hipLaunchKernelGGL(render_bwd_rays_reduce_kernel, dim3((unsigned)((a->n_rays + kRayWaves - 1) / kRayWaves)),
                      dim3(64 * kRayWaves), 0, s, r);
   return hip_status(hipGetLastError());
+}
+
+// ---- density queries (hn_density.h) ------------------------------------------
+// Every check of hn_density_points / hn_density_lattice but the point count's,
+// before any launch.
+static int32_t density_check(const hn_grid* g, const hn_mlp* w, const float* table, const float* sigma,
+                             const uint32_t* occ) {
+  if (!g || !w || !table || !mlp_ok(*w) || (!sigma && !occ)) return HN_E_NULL;
+  if (int32_t st = check_grid(g)) return st;
+  return g->n_levels != 16 ? HN_E_SHAPE : HN_OK;   // encode_tile's 16 levels
+}
+// Pack the net into the workspace and launch density_kernel<kLattice> over k.n points.
+template <bool kLattice>
+static int32_t density_launch(const hn_grid* g, const hn_mlp* w, const float* table, DensityK& k, void* workspace,
+                              size_t ws_bytes, hipStream_t s) {
+  if (!workspace) return HN_E_NULL;
+  if (ws_bytes < hn_mlp_workspace_bytes()) return HN_E_WORKSPACE;
+  float* P = (float*)workspace;
+  if (int32_t st = mlp_pack_launch(w, P, s)) return st;
+  k.g = make_grid_args(*g);
+  k.table = table;
+  k.P = P;
+  const int64_t tiles = (k.n + 31) / 32;
+  const int cus = device_cus();
+  const int64_t resident = (int64_t)(cus > 0 ? cus : 256) * kDenWgPerCu;
+  const int64_t blocks = std::min<int64_t>((tiles + kDenWaves - 1) / kDenWaves, resident);
+  hipLaunchKernelGGL(density_kernel<kLattice>, dim3((unsigned)blocks), dim3(64 * kDenWaves), 0, s, k);
+  return hip_status(hipGetLastError());
+}
+
+extern "C" int32_t hn_density_points(const hn_grid* g, const hn_mlp* w, const float* table, const float* x, int64_t n,
+                                     float threshold, float* sigma, uint32_t* occ, void* workspace, size_t ws_bytes,
+                                     void* stream) {
+  if (int32_t st = density_check(g, w, table, sigma, occ)) return st;
+  if (n < 0 || n > HN_DENSITY_MAX_POINTS) return HN_E_SHAPE;
+  if (n == 0) return HN_OK;
+  if (!x) return HN_E_NULL;
+  DensityK k{};
+  k.x = x;
+  k.n = n;
+  k.threshold = threshold;
+  k.sigma = sigma;
+  k.occ = occ;
+  return density_launch<false>(g, w, table, k, workspace, ws_bytes, (hipStream_t)stream);
+}
+
+extern "C" int32_t hn_density_lattice(const hn_grid* g, const hn_mlp* w, const float* table, const hn_lattice* lat,
+                                      float threshold, float* sigma, uint32_t* occ, void* workspace, size_t ws_bytes,
+                                      void* stream) {
+  if (!lat) return HN_E_NULL;
+  if (int32_t st = density_check(g, w, table, sigma, occ)) return st;
+  int64_t n = 1;
+  for (int a = 0; a < 3; ++a) {   // compared before the multiply: n stays <= HN_DENSITY_MAX_POINTS, no overflow
+    if (lat->dims[a] <= 0 || lat->dims[a] > HN_DENSITY_MAX_POINTS / n) return HN_E_SHAPE;
+    n *= lat->dims[a];
+  }
+  DensityK k{};
+  k.n = n;
+  for (int a = 0; a < 3; ++a) {
+    k.lo[a] = lat->lo[a];
+    k.step[a] = lat->step[a];
+  }
+  k.nx = (uint32_t)lat->dims[0];
+  k.ny = (uint32_t)lat->dims[1];
+  k.threshold = threshold;
+  k.sigma = sigma;
+  k.occ = occ;
+  return density_launch<true>(g, w, table, k, workspace, ws_bytes, (hipStream_t)stream);
 }

@@ -1275,6 +1275,134 @@ def render_views(cfg, H, W, K, poses, near, far, table, ws, ndc=False, t_vals=No
                          weights_packed, return_rays, variant, out)
 
 
+# --------------------------------------------------------------------------
+# density queries (hn_density_points / hn_density_lattice)
+# --------------------------------------------------------------------------
+def _f32x3(who, name, v):
+    """Three numbers (or a 3-element tensor) as a CPU float32 tensor."""
+    t = torch.as_tensor(v).detach().to("cpu", torch.float32).reshape(-1)
+    if t.numel() != 3:
+        raise ValueError(f"hashnerf_amd.{who}: {name} must hold 3 values, got {tuple(t.shape)}")
+    return t
+
+
+def _lattice_dims(who, dims):
+    d = tuple(int(v) for v in dims)
+    if len(d) != 3 or min(d) <= 0 or max(d) >= 1 << 31 or d[0] * d[1] * d[2] > L.DENSITY_MAX_POINTS:
+        raise ValueError(f"hashnerf_amd.{who}: dims must be (nx, ny, nz), each >= 1 and at most "
+                         f"{L.DENSITY_MAX_POINTS} points in all, got {dims!r}")
+    return d
+
+
+def lattice_coords(lo, step, dims, device=None):
+    """The points of a density lattice, [nz, ny, nx, 3] float32: point (ix, iy,
+    iz) has the coordinate lo[a] + float32(i_a) * step[a] on axis a, one float32
+    multiply and one float32 add -- the host statement of the rule
+    density_lattice's kernel follows, bit for bit."""
+    nx, ny, nz = _lattice_dims("lattice_coords", dims)
+    lo, step = _f32x3("lattice_coords", "lo", lo), _f32x3("lattice_coords", "step", step)
+    ax = [lo[a] + torch.arange(n, dtype=torch.float32) * step[a] for a, n in enumerate((nx, ny, nz))]
+    out = torch.empty((nz, ny, nx, 3), dtype=torch.float32)
+    out[..., 0] = ax[0][None, None, :]
+    out[..., 1] = ax[1][None, :, None]
+    out[..., 2] = ax[2][:, None, None]
+    return out if device is None else out.to(device)
+
+
+def unpack_occupancy(words, dims):
+    """Occupancy words (int32: bit q & 31 of word q >> 5 is point q = (iz * ny +
+    iy) * nx + ix) -> bool [nz, ny, nx], on the words' device."""
+    nx, ny, nz = _lattice_dims("unpack_occupancy", dims)
+    n = nx * ny * nz
+    words = words.reshape(-1)
+    if words.dtype != torch.int32 or words.numel() != (n + 31) // 32:
+        raise ValueError(f"hashnerf_amd.unpack_occupancy: {(n + 31) // 32} int32 words for dims {dims!r}, got "
+                         f"{words.numel()} of {words.dtype}")
+    bits = (words[:, None] >> torch.arange(32, dtype=torch.int32, device=words.device)) & 1
+    return bits.reshape(-1)[:n].bool().reshape(nz, ny, nx)
+
+
+def _density(who, grid, table, net_weights, n, threshold, want_sigma, out, call):
+    """What density_points and density_lattice share: the outputs (fresh, or the
+    caller's ``out`` = (sigma, occ)), the workspace and the call.  Returns
+    (sigma or None, occ or None)."""
+    if grid.n_levels != 16:
+        raise ValueError(f"hashnerf_amd.{who}: the density kernel covers 16-level grids, got {grid.n_levels}")
+    if threshold is None and not want_sigma:
+        raise ValueError(f"hashnerf_amd.{who}: nothing asked for (want_sigma=False needs a threshold)")
+    ws = [w.detach().contiguous() for w in net_weights]
+    if [w.numel() for w in ws] != [2048, 1024, 1984, 4096, 192]:
+        raise ValueError(f"hashnerf_amd.{who}: net_weights must be one NeRFSmall's five tensors "
+                         "(NeRFSmall.weights())")
+    table = table.detach().contiguous()
+    L.require_device(table, *ws)
+    dev = table.device
+    if table.numel() != (16 << grid.log2_hashmap_size) * 2:
+        raise ValueError(f"hashnerf_amd.{who}: table must be [16, 2^{grid.log2_hashmap_size}, 2]")
+    sigma, occ = out if out is not None else (None, None)
+    if out is None:
+        sigma = torch.empty((n,), dtype=torch.float32, device=dev) if want_sigma else None
+        occ = torch.empty(((n + 31) // 32,), dtype=torch.int32, device=dev) if threshold is not None else None
+    for t, dt, m, name in ((sigma, torch.float32, n, "sigma"), (occ, torch.int32, (n + 31) // 32, "occ")):
+        if t is not None and (t.dtype != dt or t.numel() != m or not t.is_contiguous() or t.device != dev):
+            raise ValueError(f"hashnerf_amd.{who}: out's {name} must be contiguous {dt} of {m} elements on {dev}")
+    if sigma is None and occ is None:
+        raise ValueError(f"hashnerf_amd.{who}: out holds neither sigma nor occ")
+    if occ is not None and threshold is None:
+        raise ValueError(f"hashnerf_amd.{who}: an occ output needs a threshold")
+    if n == 0:   # nothing to launch (an empty tensor's pointer is NULL: the library would refuse it)
+        return sigma, occ
+    nbytes = L.lib().hn_mlp_workspace_bytes()
+    wsb = _ws(nbytes, dev)
+    t0 = TIMER.begin(who)
+    L.check(call(grid, L.make_mlp(ws), L.ptr(table), 0.0 if threshold is None else float(threshold), L.ptr(sigma),
+                 L.ptr(occ), L.ptr(wsb), nbytes, L.stream(dev)), who)
+    TIMER.end(who, t0)
+    return sigma, occ
+
+
+def _density_result(sigma, occ):
+    return sigma if occ is None else occ if sigma is None else (sigma, occ)
+
+
+@torch.no_grad()
+def density_points(grid, table, net_weights, pts, threshold=None, want_sigma=True, out=None):
+    """hn_density_points: raw sigma (NeRFSmall's column 3, before raw2outputs'
+    ReLU) of the field (grid, table, one net's five weights) at pts [n, 3] --
+    bitwise what NeRFSmall(cat[HashEmbedder(pts), sh])[:, 3] gives, from one
+    kernel that writes nothing but the answers.  Returns sigma [n]; with a
+    threshold (sigma, occ), occ = the int32 words of sigma > threshold (bit q &
+    31 of word q >> 5; unpack_occupancy); with want_sigma=False only occ.
+    out = (sigma or None, occ or None): tensors to write into.  No autograd:
+    the outputs are detached."""
+    pts = pts.detach().contiguous()
+    L.require_device(pts)
+    if pts.dim() != 2 or pts.shape[1] != 3:
+        raise ValueError(f"hashnerf_amd.density_points: pts must be [n, 3], got {tuple(pts.shape)}")
+    n = pts.shape[0]
+    lib = L.lib()
+    call = lambda g, w, t, thr, *rest: lib.hn_density_points(g, w, t, L.ptr(pts), n, thr, *rest)
+    return _density_result(*_density("density_points", grid, table, net_weights, n, threshold, want_sigma, out, call))
+
+
+@torch.no_grad()
+def density_lattice(grid, table, net_weights, lo, step, dims, threshold=None, want_sigma=True, out=None):
+    """hn_density_lattice: density_points on lattice_coords(lo, step, dims)
+    without the points: the kernel forms each coordinate itself (bitwise
+    lattice_coords').  dims = (nx, ny, nz); returns sigma [nz, ny, nx] and / or
+    the occupancy words [(nx ny nz + 31) // 32] as density_points does (out's
+    sigma: any contiguous tensor of nx ny nz elements)."""
+    nx, ny, nz = _lattice_dims("density_lattice", dims)
+    lo, step = _f32x3("density_lattice", "lo", lo), _f32x3("density_lattice", "step", step)
+    lat = L.HnLattice()
+    for a in range(3):
+        lat.lo[a], lat.step[a], lat.dims[a] = float(lo[a]), float(step[a]), (nx, ny, nz)[a]
+    lib = L.lib()
+    call = lambda g, w, t, thr, *rest: lib.hn_density_lattice(g, w, t, lat, thr, *rest)
+    sigma, occ = _density("density_lattice", grid, table, net_weights, nx * ny * nz, threshold, want_sigma, out, call)
+    return _density_result(None if sigma is None else sigma.view(nz, ny, nx), occ)
+
+
 def render_rays_fused(cfg, rays, t_vals, t_rand, u, noise_c, noise_f, table,
                       coarse_ws: Sequence[torch.Tensor], fine_ws: Sequence[torch.Tensor], ray_grad: bool = False):
     """ray_grad: the saved state is also kept for rays that require grad and the

@@ -348,6 +348,81 @@ def render_views(H, W, K, c2w, **render_kwargs):
     return _whole_image("render_views", _views_ineligible, call, H, W, K, c2w, render_kwargs)
 
 
+unpack_occupancy = HF.unpack_occupancy
+
+
+def _density_field(who, network_fn, network_query_fn):
+    """(grid, table, weights) of a field the density kernel covers -- _fusable's
+    conditions on the embedder and the net -- else ValueError naming the reason."""
+    why = None
+    if not isinstance(network_query_fn, NetworkQuery):
+        why = "network_query_fn is not a NetworkQuery"
+    elif not isinstance(network_query_fn.embed_fn, HashEmbedder):
+        why = "the embedder is not a HashEmbedder"
+    elif network_query_fn.embed_fn.n_levels != 16:
+        why = f"the hash grid has {network_query_fn.embed_fn.n_levels} levels, not 16"
+    elif not isinstance(network_fn, NeRFSmall):
+        why = "network_fn is not a NeRFSmall"
+    if why is not None:
+        raise ValueError(f"hashnerf_amd.{who}: not eligible: {why}")
+    emb = network_query_fn.embed_fn
+    return emb.grid(), emb.table, network_fn.weights()
+
+
+def cell_centre_lattice(resolution, bmin, bmax):
+    """density_grid's lattice over the box [bmin, bmax]: resolution = n or (nx,
+    ny, nz) cells, one point at each cell's centre -- step = (bmax - bmin) / n
+    and lo = bmin + 0.5 * step, in float32 on the host.  Returns (lo, step,
+    dims): two CPU float32 tensors and (nx, ny, nz)."""
+    dims = (int(resolution),) * 3 if isinstance(resolution, (int, np.integer)) else tuple(int(v) for v in resolution)
+    if len(dims) != 3 or min(dims) <= 0:
+        raise ValueError(f"hashnerf_amd.density_grid: resolution must be n or (nx, ny, nz), each >= 1, got "
+                         f"{resolution!r}")
+    bmin = torch.as_tensor(bmin).detach().to("cpu", torch.float32).reshape(3)
+    bmax = torch.as_tensor(bmax).detach().to("cpu", torch.float32).reshape(3)
+    step = (bmax - bmin) / torch.tensor(dims, dtype=torch.float32)
+    return bmin + 0.5 * step, step, dims
+
+
+@torch.no_grad()
+def query_density(pts, network_fn, network_query_fn, threshold=None):
+    """Raw sigma of the field at pts [..., 3] -> [...]: network_fn's column 3
+    (before raw2outputs' ReLU) at each point, bitwise what network_fn(cat[
+    embed_fn(pts), sh]) gives there, from the density kernel alone
+    (functional.density_points): no colour net, nothing per point written but
+    the answer.  With a threshold: (sigma, sigma > threshold as bool [...]).
+    network_fn / network_query_fn: create_nerf's (a NeRFSmall over a NetworkQuery
+    with a 16-level HashEmbedder; anything else raises ValueError)."""
+    grid, table, ws = _density_field("query_density", network_fn, network_query_fn)
+    pts = torch.as_tensor(pts)
+    if pts.shape[-1] != 3:
+        raise ValueError(f"hashnerf_amd.query_density: pts must be [..., 3], got {tuple(pts.shape)}")
+    shape = pts.shape[:-1]
+    out = HF.density_points(grid, table, ws, pts.reshape(-1, 3), threshold=threshold)
+    if threshold is None:
+        return out.reshape(shape)
+    sigma, occ = out
+    if sigma.numel() == 0:   # no points: no words to unpack
+        return sigma.reshape(shape), torch.empty(shape, dtype=torch.bool, device=sigma.device)
+    return sigma.reshape(shape), HF.unpack_occupancy(occ, (sigma.numel(), 1, 1)).reshape(shape)
+
+
+@torch.no_grad()
+def density_grid(resolution, network_fn, network_query_fn, bounds=None, threshold=None, want_sigma=True):
+    """Raw sigma of the field on a regular lattice, for meshing or an
+    occupancy grid: resolution = n or (nx, ny, nz) cells over bounds = (min,
+    max) (default: the embedder's bounding box), one point at each cell's
+    centre (cell_centre_lattice).  The kernel forms the points itself
+    (functional.density_lattice).  Returns sigma [nz, ny, nx]; with a threshold
+    (sigma, words), words = the packed int32 occupancy sigma > threshold
+    (unpack_occupancy(words, dims) -> bool [nz, ny, nx]); with want_sigma=False
+    only the words (1 bit per point written)."""
+    grid, table, ws = _density_field("density_grid", network_fn, network_query_fn)
+    bmin, bmax = network_query_fn.embed_fn.box() if bounds is None else bounds
+    lo, step, dims = cell_centre_lattice(resolution, bmin, bmax)
+    return HF.density_lattice(grid, table, ws, lo, step, dims, threshold=threshold, want_sigma=want_sigma)
+
+
 _IMAGE_GROUP = 8    # views per render_views launch of render_path: bounds the output buffers
 
 

@@ -779,6 +779,41 @@ size_t  hn_render_views_workspace_bytes(const hn_render_cfg* cfg);
 int32_t hn_render_views(const hn_render_cfg* cfg, const hn_view_args* a, void* workspace, size_t ws_bytes,
                         void* stream);
 
+/* ---- density queries (additive under ABI 14) -------------------------------
+ * Raw sigma of one NeRFSmall over the hash grid -- NeRFSmall's column 3, the
+ * value before the ReLU that raw2outputs applies -- at n points x [n][3], or
+ * on a regular lattice the kernel generates itself: point q = (iz * ny + iy)
+ * * nx + ix has the coordinate lo[a] + (float)i_a * step[a] on axis a, formed
+ * as one f32 multiply and one f32 add (no FMA), so lo + arange(n, float32) *
+ * step on the host gives the same bits.  Only the hash encoding and the two
+ * sigma layers run; a point's sigma is bitwise what hn_encode_fwd + hn_mlp_fwd
+ * (and the fused forward) give for it.  Outputs, each optional, at least one:
+ *   sigma [n] f32;
+ *   occ [(n + 31) / 32] u32: bit q & 31 of word q >> 5 = sigma[q] > threshold,
+ *   the last word's bits past n are 0 (threshold is read only with occ).
+ * Nothing is accumulated: a second call writes the same bits.  The grid must
+ * have 16 levels; n and nx * ny * nz are at most HN_DENSITY_MAX_POINTS (2^31
+ * tiles of 32 points).  workspace: hn_mlp_workspace_bytes() bytes, the net's
+ * packed copy, written by the call.  Status, every check before any launch:
+ * HN_E_NULL for a NULL g, w (or one of its tensors), table, lat, x (n > 0),
+ * workspace, or both outputs NULL; HN_E_SHAPE for a grid that is not 16 levels
+ * x 2 features with T in 1..24, n < 0, a dim <= 0 or a count past the bound;
+ * HN_E_WORKSPACE for a short workspace.  n == 0 is HN_OK and launches nothing.
+ * The library does not allocate or synchronise. */
+#define HN_DENSITY_MAX_POINTS ((int64_t)1 << 36)
+typedef struct hn_lattice {
+  float lo[3];
+  float step[3];
+  int32_t dims[3];                /* nx, ny, nz */
+  int32_t reserved;
+} hn_lattice;
+int32_t hn_density_points(const hn_grid* g, const hn_mlp* w, const float* table, const float* x, int64_t n,
+                          float threshold, float* sigma, uint32_t* occ, void* workspace, size_t ws_bytes,
+                          void* stream);
+int32_t hn_density_lattice(const hn_grid* g, const hn_mlp* w, const float* table, const hn_lattice* lat,
+                           float threshold, float* sigma, uint32_t* occ, void* workspace, size_t ws_bytes,
+                           void* stream);
+
 #ifdef __cplusplus
 }
 #endif
